@@ -14,8 +14,8 @@ verdict.  --inflight (default 2) submissions run at once on separate streams (st
 stream k mod 2), as the coalescer keeps two leaders per device: one step's serial tail
 (Horner, final exponentiation) overlaps the next step's hash_to_G2.  Inputs are resident in HBM (decompressed points, as blst takes them);
 hash_to_G2 of every message, both scalar sides, the Miller products and the final
-exponentiations all run inside the timed region.  The same run also times ONE batch per
-step ("single_batch": the 4096-set latency view).
+exponentiations all run inside the timed region.  With --full the same run also times ONE
+batch per step ("single_batch": the 4096-set latency view).
 
 Other legs (--config): C3 sync-committee fast_aggregate_verify (10,000 messages x 512
 registry keys; unit = messages), C4 an epoch of attestations (2,048 committees over a
@@ -30,10 +30,19 @@ all-gathered over xGMI, and every rank runs ONE final exponentiation over the pr
 2048 committees split into whole committees per rank) and C5 (2^20 sets in total) are strong
 scaling; C3 needs no exchange (per-message verdicts).
 
-Extra JSON fields: "roofline" (dominant kernel's integer-multiply throughput vs the
-measured v_mad_u64_u32 peak, HIP events on the launch stream, W frozen in BASELINE.md 4)
-and "cpu_baseline" (the C restatement of blst's multi-verify built with BLS_REF_FAST, timed on
-this host's cores).
+A plain run sets up, warms up, times --steps steps and prints the result line; nothing else.
+--full adds the legs that take runs or measurements of their own: per-stage HIP-event timing
+inside the timed region and the "roofline" field (dominant kernel's integer-multiply throughput
+vs the measured v_mad_u64_u32 peak, W frozen in BASELINE.md 4), "cpu_baseline" (the C
+restatement of blst's multi-verify built with BLS_REF_FAST, timed on this host's cores), C2's
+"single_batch" leg, C4's per-committee check, and every C1 leg beside the block's finish
+latency (the two-call and point-list forms, single checks, gossip batches, the load legs).
+
+--dump-outputs DIR writes what the last timed step handed its caller as DIR/<name>.npy
+(float64, one row per item: [1 if verified else 0, the engine's status code]): "verdicts"
+(C2/C4/C5: one row per batch; C3: one per message; ranks other than 0 write
+verdicts_rank<r>), C1: "verdicts" (the call's) and "set_status" (one row per signature: decoded,
+its code).  The inputs are seeded, so two builds run with the same arguments see the same bytes.
 """
 
 import argparse
@@ -140,6 +149,19 @@ def to_i64(vals):
     return [v - (1 << 64) if v >= 1 << 63 else v for v in vals]
 
 
+def dump_outputs(path, arrays):
+    """--dump-outputs: each status array the last timed step returned, as path/<name>.npy in
+    float64, one row per item: column 0 is the answer the reference's caller gets (1 = verified /
+    decoded, 0 = not; Signature::multi_verify returns that bool), column 1 the engine's status
+    code (0 = GBLS_SUCCESS).  An accepted item is therefore a nonzero row, and a buffer the step
+    never wrote (the -1 fill) or a zeroed one cannot pass for it."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        codes = np.asarray(a, dtype=np.float64).reshape(-1)
+        np.save(os.path.join(path, name + ".npy"), np.stack([(codes == 0).astype(np.float64), codes], axis=1))
+
+
 class Leg:
     """One benchmark config: device-resident inputs + a step() that enqueues one pass."""
     metric = "verified BLS signature sets/sec (whole node)"
@@ -173,11 +195,17 @@ def main():
                          "shard shape) and report the node rate that shape predicts (DESIGN.md 5)")
     ap.add_argument("--load-threads", type=int, default=16,
                     help="C1: gossip threads of the concurrent window and of the block-under-load legs")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: per-stage timing and the roofline, "
+                         "the CPU baseline, C2's single-batch leg, C4's per-committee check, C1's other legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them returned as DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-stages", action="store_true",
-                    help="no per-stage HIP-event timing in the timed region (roofline stage times absent)")
+                    help="--full: no per-stage HIP-event timing in the timed region (roofline stage times absent)")
     ap.add_argument("--no-single", action="store_true",
-                    help="C2: skip the one-batch-per-step leg (PMC passes then see only the 16-batch launches)")
+                    help="--full, C2: skip the one-batch-per-step leg (PMC passes then see only the 16-batch "
+                         "launches)")
     ap.add_argument("--tuning", action="store_true",
                     help="let the engine read its GBLS_* tuning environment variables (sweeps)")
     args = ap.parse_args()
@@ -414,7 +442,10 @@ def main():
     D = max(1, args.inflight)
     streams = [torch.cuda.Stream() for _ in range(D)] if D > 1 else None
 
+    last_slot = [0]  # the slot whose buffers hold the most recent step's outputs
+
     def run(k):
+        last_slot[0] = k % D
         if streams is None:
             step()
             return
@@ -441,7 +472,7 @@ def main():
         raise SystemExit("verdicts of the warm-up step are WRONG")
 
     L.gbls_profile_reset()
-    L.gbls_profile(0 if args.no_stages else 1)
+    L.gbls_profile(1 if args.full and not args.no_stages else 0)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -467,9 +498,13 @@ def main():
     if not ok:
         raise SystemExit("verdicts changed during the timed region")
 
+    if args.dump_outputs:
+        v_last = (d_vs if cfg == "C3" else d_verdicts)[last_slot[0]]
+        dump_outputs(args.dump_outputs, {"verdicts" if rank == 0 else "verdicts_rank%d" % rank: v_last.cpu().numpy()})
+
     # ---- C4: every committee's own verdict (each committee one segment), on every rank
     committee_check = None
-    if cfg == "C4":
+    if cfg == "C4" and args.full:
         segc = G.u32_array(range(n + 1))
         vc = torch.full((n,), -1, dtype=torch.int32, device=dev)
         G.check(L.gbls_multi_verify_indexed_segments_device(ptr(d_msgs), ptr(d_sigs), ptr(d_idx), ptr(d_off),
@@ -486,7 +521,7 @@ def main():
 
     # ---- one batch per step (the 4096-set latency view), same inputs, after the main timing
     single = None
-    if cfg == "C2" and world == 1 and leg.segments > 1 and not args.no_single:
+    if args.full and cfg == "C2" and world == 1 and leg.segments > 1 and not args.no_single:
         per = leg.units // leg.segments
         seg1 = G.u32_array([0, per])
         v1 = torch.full((1,), -1, dtype=torch.int32, device=dev)
@@ -506,13 +541,14 @@ def main():
         single = {"batches_per_step": 1, "sets_per_step": per, "value": round(per * args.steps / d1, 1),
                   "ms_per_step": round(d1 / args.steps * 1e3, 4)}
 
-    # ---- roofline of the dominant kernel (HIP events on the launch stream)
+    # ---- roofline of the dominant kernel (HIP events on the launch stream); --full only: a plain
+    # run records no stage events, so it has no stages, no dominant kernel and measures no peak
     nst = 32
     ms = (ctypes.c_double * nst)()
     calls = (ctypes.c_uint32 * nst)()
     ns = L.gbls_profile_read(ms, calls, nst)
     stages = {L.gbls_stage_name(i).decode(): (ms[i], calls[i]) for i in range(ns) if calls[i]}
-    peak = L.gbls_measure_mad64_peak()
+    peak = L.gbls_measure_mad64_peak() if args.full else 0.0
     # dominant kernel: the single-kernel stage with the most algorithmic work per step
     # (W x units; rocprofv3 reports the same kernel's duration).  Not by wall time: with two
     # submissions in flight a low-priority side-stream stage (k_mv_g1mul) spans most of a
@@ -548,7 +584,7 @@ def main():
         total_units = leg.epoch["committees"] if cfg == "C4" else world * leg.units
         value = total_units * args.steps / dt
         cpu = None
-        if not args.no_cpu and world == 1 and cfg == "C2":
+        if args.full and not args.no_cpu and world == 1 and cfg == "C2":
             cpu = cpu_baseline(args.cpu_sample, args.cpu_threads or cpu_threads())
         line = {"metric": leg.metric, "value": round(value, 1),
                 "unit": leg.unit, "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -612,10 +648,14 @@ def bench_c1(args, L, G, F, np):
 
     pidx, poff = idx.ctypes.data_as(ctypes.c_void_p), off.ctypes.data_as(ctypes.c_void_p)
 
+    last = {}  # what the most recent finish() handed back: the call's status, each signature's
+
     def finish():  # one submission: device decompression fused into the batch verify
         st = G.i32_array(n)
-        return L.gbls_multi_verify_compressed(msgs, comp_sigs, None, pidx, poff,
-                                              (ctypes.c_uint64 * n)(*rands), n, st)
+        rc = L.gbls_multi_verify_compressed(msgs, comp_sigs, None, pidx, poff,
+                                            (ctypes.c_uint64 * n)(*rands), n, st)
+        last["verdicts"], last["set_status"] = [rc], st
+        return rc
 
     def finish_two_calls():  # decompress, then verify (two submissions)
         dec = ctypes.create_string_buffer(192 * n)
@@ -634,6 +674,23 @@ def bench_c1(args, L, G, F, np):
             out.append(time.perf_counter() - t)
         return sorted(out)
 
+    lat = timed(finish)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
+    line = {"metric": "MultiVerifier::finish latency, mainnet-shaped block (C1)", "value": round(lat[len(lat) // 2] * 1e3, 3),
+            "unit": "ms (p50)", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(sum(lat) / len(lat) * 1e3, 3), "higher_is_better": False, "scaling": "n/a",
+            "vs_baseline": None, "dtype": DTYPE,
+            "data": "synthetic (seeded registry, committees and messages)",
+            "config": {"workload": "C1: %d sets (%d keys aggregated from the registry), 96-byte signatures "
+                                   "decompressed on the device inside the verify submission, host pointers, PCIe "
+                                   "included" % (n, int(off[-1])), "config": "C1"},
+            "p99_ms": round(lat[min(len(lat) - 1, int(len(lat) * 0.99))] * 1e3, 3),
+            "roofline": None, "cpu_baseline": None}
+    if not args.full:  # the headline leg only
+        print(json.dumps(line), flush=True)
+        return
+
     # the Rust drop-in's form (rust/bls_patch/verifier.rs): deferred Triple key LISTS handed over
     # as points + per-set offsets, summed on the device inside the same submission
     pts = F.public_keys([sks[int(i)] for i in idx])
@@ -643,7 +700,6 @@ def bench_c1(args, L, G, F, np):
         return L.gbls_multi_verify_compressed_ex(msgs, comp_sigs, pts, None, poff,
                                                  (ctypes.c_uint64 * n)(*rands), n, st, 0)
 
-    lat = timed(finish)
     lat2 = timed(finish_two_calls)
     latp = timed(finish_points)
     # single checks at n = 1 (SingleVerifier, sync-committee messages and contributions):
@@ -777,15 +833,7 @@ def bench_c1(args, L, G, F, np):
     bt.join()
     assert not errs
     glat_b.sort()
-    line = {"metric": "MultiVerifier::finish latency, mainnet-shaped block (C1)", "value": round(lat[len(lat) // 2] * 1e3, 3),
-            "unit": "ms (p50)", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(sum(lat) / len(lat) * 1e3, 3), "higher_is_better": False, "scaling": "n/a",
-            "vs_baseline": None, "dtype": DTYPE,
-            "data": "synthetic (seeded registry, committees and messages)",
-            "config": {"workload": "C1: %d sets (%d keys aggregated from the registry), 96-byte signatures "
-                                   "decompressed on the device inside the verify submission, host pointers, PCIe "
-                                   "included" % (n, int(off[-1])), "config": "C1"},
-            "p99_ms": round(lat[min(len(lat) - 1, int(len(lat) * 0.99))] * 1e3, 3),
+    line.update({
             "decompress_then_verify_p50_ms": round(lat2[len(lat2) // 2] * 1e3, 3),
             "points_pk_off": {"p50_ms": round(latp[len(latp) // 2] * 1e3, 3),
                               "p99_ms": round(latp[min(len(latp) - 1, int(len(latp) * 0.99))] * 1e3, 3),
@@ -806,8 +854,7 @@ def bench_c1(args, L, G, F, np):
             "gossip64_under_back_to_back_blocks": {
                 "p50_ms": round(glat_b[len(glat_b) // 2] * 1e3, 3),
                 "p99_ms": round(glat_b[min(len(glat_b) - 1, int(len(glat_b) * 0.99))] * 1e3, 3),
-                "load": "one thread importing the C1 block (GBLS_CALL_BLOCK) back to back"},
-            "roofline": None, "cpu_baseline": None}
+                "load": "one thread importing the C1 block (GBLS_CALL_BLOCK) back to back"}})
     print(json.dumps(line), flush=True)
 
 

@@ -51,7 +51,7 @@ def test_bench_two_rank_c4_epoch_strong_scaling():
     committees over a 2^20-key registry) split into whole committees per rank (1024 each), the
     ranks' Miller partials all-gathered into one final exponentiation, strong scaling; the bench
     then checks every committee's own verdict on its rank and sums them over the ranks."""
-    args = [os.path.join(ROOT, "bench.py"), "--config", "C4", "--gpus", "2", "--steps", "2", "--warmup", "1",
+    args = [os.path.join(ROOT, "bench.py"), "--config", "C4", "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
             "--no-cpu"]
     r = _run(args, 600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]

@@ -11,8 +11,8 @@ i=0
 for rep in 1 2; do
 for cfg in "$@"; do
   i=$((i + 1))
-  env $cfg timeout -k 10 200 python bench.py --steps 10 --warmup 3 --no-cpu --tuning > $O/ab_$i.txt 2>&1 || exit $?
-  env $cfg timeout -k 10 200 python bench.py --config C4 --steps 10 --warmup 2 --no-cpu --tuning > $O/ab4_$i.txt 2>&1 || exit $?
+  env $cfg timeout -k 10 200 python bench.py --full --steps 10 --warmup 3 --no-cpu --tuning > $O/ab_$i.txt 2>&1 || exit $?
+  env $cfg timeout -k 10 200 python bench.py --full --config C4 --steps 10 --warmup 2 --no-cpu --tuning > $O/ab4_$i.txt 2>&1 || exit $?
   echo "$cfg :: C2 $(grep -o '"value": [0-9.]*' $O/ab_$i.txt | head -1) single $(grep -o '"single_batch": {[^}]*}' $O/ab_$i.txt | grep -o '"value": [0-9.]*') C4 $(grep -o '"value": [0-9.]*' $O/ab4_$i.txt | head -1)" | tee -a $O/ab.txt
 done
 done

@@ -8,7 +8,7 @@ mkdir -p $O
 export TMPDIR=/tmp
 for r in 1 2 3; do
   for h in 0 1; do
-    GBLS_SIDE2_HIGH=$h timeout -k 10 300 python bench.py --config C4 --steps 10 --warmup 2 --no-cpu > $O/c4_h${h}_$r.txt 2>&1 || exit $?
+    GBLS_SIDE2_HIGH=$h timeout -k 10 300 python bench.py --full --config C4 --steps 10 --warmup 2 --no-cpu > $O/c4_h${h}_$r.txt 2>&1 || exit $?
     echo "side2_high $h rep $r $(grep -o '"value": [0-9.]*' $O/c4_h${h}_$r.txt | head -1) $(grep -o '"k_g2sum": [0-9.]*' $O/c4_h${h}_$r.txt | head -1) $(grep -o '"k_h2c_clear": [0-9.]*' $O/c4_h${h}_$r.txt | head -1)" | tee -a $O/summary.txt
   done
 done

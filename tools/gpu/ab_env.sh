@@ -10,6 +10,6 @@ export TMPDIR=/tmp
 i=0
 for cfg in "$@"; do
   i=$((i + 1))
-  env $cfg timeout -k 10 200 python bench.py --steps 10 --warmup 3 --no-cpu --tuning > $O/ab_$i.txt 2>&1 || exit $?
+  env $cfg timeout -k 10 200 python bench.py --full --steps 10 --warmup 3 --no-cpu --tuning > $O/ab_$i.txt 2>&1 || exit $?
   echo "$cfg :: $(grep -o '"value": [0-9.]*' $O/ab_$i.txt | head -1) single $(grep -o '"single_batch": {[^}]*}' $O/ab_$i.txt | grep -o '"value": [0-9.]*')" >> $O/ab.txt
 done

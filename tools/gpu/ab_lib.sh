@@ -12,8 +12,8 @@ tail -1 $O/pytest_gpu.txt
 for r in 1 2 3; do
   for m in new prev; do
     if [ $m = prev ]; then export GBLS_LIB=$PREV; else unset GBLS_LIB; fi
-    timeout -k 10 300 python bench.py --config C4 --steps 10 --warmup 2 --no-cpu > $O/c4_${m}_$r.txt 2>&1 || exit $?
-    timeout -k 10 400 python bench.py --config C1 --steps 40 --warmup 5 > $O/c1_${m}_$r.txt 2>&1 || exit $?
+    timeout -k 10 300 python bench.py --full --config C4 --steps 10 --warmup 2 --no-cpu > $O/c4_${m}_$r.txt 2>&1 || exit $?
+    timeout -k 10 400 python bench.py --full --config C1 --steps 40 --warmup 5 > $O/c1_${m}_$r.txt 2>&1 || exit $?
     echo "$m rep $r C4 $(grep -o '"value": [0-9.]*' $O/c4_${m}_$r.txt | head -1) g2sum $(grep -o '"k_g2sum": [0-9.]*' $O/c4_${m}_$r.txt | head -1) C1 $(grep -o '"value": [0-9.]*' $O/c1_${m}_$r.txt | head -1) $(grep -o '"gossip64": {[^,]*' $O/c1_${m}_$r.txt)" | tee -a $O/summary.txt
   done
 done

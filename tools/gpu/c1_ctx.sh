@@ -8,7 +8,7 @@ O=gpurun_out/$T
 mkdir -p $O
 export TMPDIR=/tmp
 for i in $(seq 1 $N); do
-  GBLS_TRACE_STALLS=1 timeout -k 10 300 python bench.py --config C1 --steps 40 --warmup 5 > $O/c1_$i.txt 2> $O/c1_$i.err || exit $?
+  GBLS_TRACE_STALLS=1 timeout -k 10 300 python bench.py --config C1 --full --steps 40 --warmup 5 > $O/c1_$i.txt 2> $O/c1_$i.err || exit $?
   echo "run $i ctx_created $(grep -c 'creates ctx' $O/c1_$i.err) block $(grep -c 'class 1' $O/c1_$i.err) $(grep -o '"block_under_gossip_load": {[^}]*}' $O/c1_$i.txt)" | tee -a $O/summary.txt
   grep 'creates ctx' $O/c1_$i.err > $O/c1_${i}_ctx.txt || true
   rm -f $O/c1_$i.err
