@@ -31,6 +31,7 @@ if _override:
 INIT_TUNING = 0x200
 INIT_PER_CHECK = 0x400  # grouped single checks off (deterministic per-check verdicts)
 INIT_NO_COALESCE = 0x100  # cross-caller coalescing off
+INIT_DEDUP = 0x800  # batch verification grouped by message (one hash and pairing per distinct message)
 _tuning = False
 
 

@@ -78,6 +78,19 @@ class SecretKeyBytes(bytes):
         return super().__new__(cls, data)
 
 
+# ----------------------------------------------------------------------------- engine policy
+POLICY_NO_COALESCE = G.INIT_NO_COALESCE
+POLICY_PER_CHECK = G.INIT_PER_CHECK
+POLICY_DEDUP = G.INIT_DEDUP
+
+
+def set_policy(flags: int) -> int:
+    """gbls_set_policy: sets the engine's policy bits outright and returns the previous ones.
+    `set_policy(POLICY_DEDUP)` makes every batch verification group its sets by message (one
+    hash_to_G2 and one pairing per distinct message; verdicts unchanged)."""
+    return int(G.load_library().gbls_set_policy(int(flags)))  # needs no device
+
+
 # ----------------------------------------------------------------------------- batched helpers
 def decompress_public_keys(items: Sequence[bytes], validate: bool = True):
     """Batched PublicKey::try_from: returns [(status, affine96 or None)]."""

@@ -604,5 +604,47 @@ HD void g1s_from_jac28(g1s &r, const g1j28 &p) {
   to_fp(r.y, p.y);
 }
 
+// ---------------------------------------------------------------- message groups (k_g1s_msgsum)
+// A line-evaluation point (bls_pairing.h g1s, homogeneous (x : y : c)) in this layer, and
+// their complete addition (bls_pairing.h g1h_add_rcb over r28::fe).  A point is loaded without
+// a product: the engine-form limbs repacked (load12) are the coordinates times 2^-8 in this
+// layer's form, the same projective point.  Coordinates stay normalized and < 1.03 p.
+struct g1h28 {
+  fe x, y, c;
+};
+HD void f_mul12(fe &r, const fe &a) { mulk_r(r, a, 12); }
+HD void g1h28_load(g1h28 &r, const g1s &p) {
+  load12(r.x, p.x);
+  load12(r.y, p.y);
+  load12(r.c, p.c);
+}
+HD void g1h28_set_inf(g1h28 &r) {
+  f_zero(r.x);
+  f_zero(r.y);
+  f_zero(r.c);
+}
+// engine form, canonical; infinity (c = 0) all-zero
+HD void g1h28_store(g1s &r, const g1h28 &p) {
+  if (is_zero(p.c)) {
+    fp_zero(r.x);
+    fp_zero(r.y);
+    fp_zero(r.c);
+    return;
+  }
+  to_fp(r.x, p.x);
+  to_fp(r.y, p.y);
+  to_fp(r.c, p.c);
+}
+// r = a + b as bls_pairing.h g1s_add: every case, c = 0 (whatever x, y hold) for infinity.
+// r may alias a or b.
+HD void g1h28_add(g1h28 &r, const g1h28 &a, const g1h28 &b) {
+  const bool ai = is_zero(a.c), bi = is_zero(b.c);
+  g1h28 o;
+  g1h_add_rcb(o.x, o.y, o.c, a.x, a.y, a.c, b.x, b.y, b.c);
+  if (ai) o = b;
+  if (bi && !ai) o = a;
+  r = o;
+}
+
 }  // namespace r28
 }  // namespace gbls

@@ -150,6 +150,77 @@ HD void g1s_from_aff(g1s &r, const g1a &a) {
   else
     fp_one(r.c);
 }
+// (x, y, c) is the homogeneous projective point (x : y : c) of y^2 c = x^3 + 4 c^3, so two
+// such points add directly (message groups, k_g1s_msgsum): the complete addition of Renes,
+// Costello and Batina (EUROCRYPT 2016, algorithm 7: a = 0, b3 = 3 b = 12), 12 products.  It is
+// exception-free on a curve without points of order 2 (#E(Fp) = h r is odd): equal inputs,
+// opposite inputs (result (0 : y : 0)) and (0 : 1 : 0) all go through it; only this
+// engine's all-zero encoding of infinity is not a projective point, so the callers below take
+// it apart.  Over any coordinate field with f_add / f_sub / f_mul / f_mul12; outputs may alias
+// inputs.
+HD void f_mul12(fp &r, const fp &a) {
+  fp t;
+  fp_add(t, a, a);
+  fp_add(t, t, a);
+  fp_add(t, t, t);
+  fp_add(r, t, t);
+}
+template <class F>
+HD void g1h_add_rcb(F &X3, F &Y3, F &Z3, const F &X1, const F &Y1, const F &Z1, const F &X2,
+                    const F &Y2, const F &Z2) {
+  F t0, t1, t2, t3, t4, x3, y3, z3;
+  f_mul(t0, X1, X2);
+  f_mul(t1, Y1, Y2);
+  f_mul(t2, Z1, Z2);
+  f_add(t3, X1, Y1);
+  f_add(t4, X2, Y2);
+  f_mul(t3, t3, t4);
+  f_add(t4, t0, t1);
+  f_sub(t3, t3, t4);  // X1 Y2 + X2 Y1
+  f_add(t4, Y1, Z1);
+  f_add(x3, Y2, Z2);
+  f_mul(t4, t4, x3);
+  f_add(x3, t1, t2);
+  f_sub(t4, t4, x3);  // Y1 Z2 + Y2 Z1
+  f_add(x3, X1, Z1);
+  f_add(y3, X2, Z2);
+  f_mul(x3, x3, y3);
+  f_add(y3, t0, t2);
+  f_sub(y3, x3, y3);  // X1 Z2 + X2 Z1
+  f_add(x3, t0, t0);
+  f_add(t0, x3, t0);  // 3 X1 X2
+  f_mul12(t2, t2);    // b3 Z1 Z2
+  f_add(z3, t1, t2);
+  f_sub(t1, t1, t2);
+  f_mul12(y3, y3);
+  f_mul(x3, t4, y3);
+  f_mul(t2, t3, t1);
+  f_sub(x3, t2, x3);
+  f_mul(y3, y3, t0);
+  f_mul(t1, t1, z3);
+  f_add(y3, t1, y3);
+  f_mul(t0, t0, t3);
+  f_mul(z3, z3, t4);
+  f_add(z3, z3, t0);
+  X3 = x3;
+  Y3 = y3;
+  Z3 = z3;
+}
+// r = a + b, complete: doubling, opposite points, either or both inputs at infinity (c = 0);
+// an infinite sum is all-zero.  r may alias a or b.
+HD void g1s_add(g1s &r, const g1s &a, const g1s &b) {
+  const bool ai = fp_is_zero(a.c), bi = fp_is_zero(b.c);
+  g1s o;
+  g1h_add_rcb(o.x, o.y, o.c, a.x, a.y, a.c, b.x, b.y, b.c);
+  if (ai) o = b;
+  if (bi && !ai) o = a;
+  if (fp_is_zero(o.c)) {
+    fp_zero(o.x);
+    fp_zero(o.y);
+    fp_zero(o.c);
+  }
+  r = o;
+}
 HD void line_eval_s(sp034 &s, const fp2 &L0, const fp2 &L2, const fp2 &L3, const g1s &P) {
   if (fp_is_zero(P.c)) {
     fp2_one(s.a0);

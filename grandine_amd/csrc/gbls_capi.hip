@@ -35,6 +35,7 @@
 
 #include "../../include/grandine_bls_gpu.h"
 #include "gbls_common.h"
+#include "gbls_dedup.h"
 #include "gbls_sched.h"
 #include "gbls_tables.h"
 
@@ -58,6 +59,7 @@ uint32_t gbls::g_lane_r28 = 1;
 uint32_t gbls::g_lane_min = gbls::kLaneRegimeSets;
 uint32_t gbls::g_clear_staged = 0;
 uint32_t gbls::g_map_rows_max = 2048;
+uint32_t gbls::g_msgsum_wave_min = gbls::kMsgsumWaveMin;
 
 namespace {
 
@@ -121,12 +123,12 @@ struct Buf {
 // ---- optional per-stage timing (HIP events on the launch stream), for bench.py
 enum Stage {
   S_H2C_FIELD, S_H2C_MAP, S_H2C_CLEAR, S_G1MUL, S_G2MUL, S_G2SUM, S_LINES, S_LINES_S, S_ML_LEAF,
-  S_ML_REDUCE, S_ML_HORNER, S_FINAL, S_PK_GATHER, S_MSM, S_COUNT
+  S_ML_REDUCE, S_ML_HORNER, S_FINAL, S_PK_GATHER, S_MSM, S_MSGSUM, S_COUNT
 };
 const char *kStageNames[S_COUNT] = {"k_h2c_field", "k_h2c_map",   "k_h2c_clear", "k_mv_g1mul",
                                     "k_mv_g2mul",  "k_g2sum",      "k_lines",     "k_lines_S",
                                     "k_ml_group",  "k_ml_reduce",  "k_ml_horner", "k_final_verdict",
-                                    "k_pk_resolve", "k_msm"};
+                                    "k_pk_resolve", "k_msm",        "k_g1s_msgsum"};
 
 // GBLS_TRACE_STALLS=1: report host waits inside device entry points (diagnostics); every line
 // carries the call index (leases since gbls_init) and whether the lease created its context
@@ -138,6 +140,14 @@ static bool trace_stalls() {
   return on;
 }
 std::atomic<unsigned long long> g_lease_calls{0};
+// GBLS_TRACE_DEDUP=1: one line per submission that ran on message groups (GBLS_INIT_DEDUP)
+static bool trace_dedup() {
+  static const bool on = [] {
+    const char *e = std::getenv("GBLS_TRACE_DEDUP");
+    return e && *e == '1';
+  }();
+  return on;
+}
 
 // Workspaces grow by stream-ordered allocation (hipMallocAsync / hipFreeAsync from the device's
 // default pool) when the device supports it: a growth never waits on the host and never frees
@@ -233,12 +243,17 @@ struct Ctx {
   bool used = false;                  // last_stream is meaningful
   hipStream_t last_stream = nullptr;  // main stream of the previous call
   Buf in0, in1, in2, in3, in4, in5, U, Q, H, P, Pc, R, Sj, gpart, lines, Ts, V0, V1, V28, hparts, tab, part, err, out0,
-      out1, pks, pre, pre2, msm, sigd, sigst, rnd, ng1, gerr, gv, redo, rtab;
+      out1, pks, pre, pre2, msm, sigd, sigst, rnd, ng1, gerr, gv, redo, rtab, in6, Pset;
   // per-call option of the next pipeline_partials on this lease: compressed signatures
   // (96 B each, device) to decompress on the signature-side stream into `sigs`, with their
   // BLST_ERROR statuses (device) failing their segments (consumed and reset by the pipeline)
   const uint8_t *sig_c = nullptr;
   int32_t *sig_st = nullptr;
+  // per-call option of the next pipeline_partials on this lease: the batch's message groups
+  // (GBLS_INIT_DEDUP; the plan on the host, its CSR [grp_off (U + 1)][grp_set (n)] in in6, and
+  // the U unique messages in place of the n messages); consumed and reset by the pipeline
+  const dedup::Plan *plan = nullptr;
+  dedup::Plan plan_host;  // the plan object of this context's calls (its vectors keep their memory)
   // Pinned staging for host tables and host inputs: a ring of kStageRing buffers, one per call,
   // each recycled only once the uploads of the call that used it have landed.  (One buffer made
   // every call wait on the host for the previous call's uploads, which are queued behind that
@@ -482,6 +497,7 @@ struct Engine {
   size_t reg_n = 0;
   std::atomic<bool> coalesce{true};
   std::atomic<bool> per_check{false};  // GBLS_INIT_PER_CHECK: no grouped single checks
+  std::atomic<bool> dedup{false};      // GBLS_INIT_DEDUP: host batches grouped by message
   size_t msm_min = kMsmMinPerSeg;  // segments at least this large use the bucket MSM
   size_t line_budget = kLineBudget; // line-coefficient buffer bound per submission (bytes)
   uint32_t ml_g = 0;                // forced k_ml_group group size (0: chosen per launch)
@@ -552,6 +568,7 @@ bool engine_init(uint32_t device_mask, uint32_t flags) {
   // not undo an operator's or a spec-test harness's choice); gbls_set_policy sets them outright
   if (flags & GBLS_INIT_NO_COALESCE) g.coalesce.store(false);
   if (flags & GBLS_INIT_PER_CHECK) g.per_check.store(true);
+  if (flags & GBLS_INIT_DEDUP) g.dedup.store(true);
   if (g.ready.load()) return true;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(GBLS_ERR_NO_DEVICE);
@@ -586,6 +603,8 @@ bool engine_init(uint32_t device_mask, uint32_t flags) {
     if (const char *e = std::getenv("GBLS_LANE_R28")) g_lane_r28 = (uint32_t)std::strtoul(e, nullptr, 10);
     if (const char *e = std::getenv("GBLS_CLEAR_STAGED")) g_clear_staged = (uint32_t)std::strtoul(e, nullptr, 10);
     if (const char *e = std::getenv("GBLS_MAP_ROWS_MAX")) g_map_rows_max = (uint32_t)std::strtoul(e, nullptr, 10);
+    if (const char *e = std::getenv("GBLS_MSGSUM_WAVE_MIN"))
+      g_msgsum_wave_min = std::max(1u, (uint32_t)std::strtoul(e, nullptr, 10));
     if (const char *e = std::getenv("GBLS_LANE_MIN")) g_lane_min = std::max(1u, (uint32_t)std::strtoul(e, nullptr, 10));
     if (const char *e = std::getenv("GBLS_CU_SPLIT_MAX"))
       g.cu_split_max = (uint32_t)std::strtoul(e, nullptr, 10);
@@ -789,6 +808,18 @@ void ml_tail(Ctx &c, hipStream_t st, const MlTables &mt, const uint32_t *T, uint
   launch_ml_horner(st, cur, nms, partials, nullptr, 0, tmp);
 }
 
+// a batch takes the bucket MSM for S when it has random scalars and every segment is large
+bool msm_regime(bool rands, size_t n, const uint32_t *seg_off, size_t nseg) {
+  bool msm = rands && n > 0;
+  for (size_t s = 0; msm && s < nseg; s++) msm = seg_off[s + 1] - seg_off[s] >= g.msm_min;
+  return msm;
+}
+// whether a submission of nq set-side pairs keeps all 68 line events of every pair resident
+bool lines_unsliced(size_t nq, size_t n, const uint32_t *seg_off, size_t nseg) {
+  const size_t X = msm_regime(true, n, seg_off, nseg) ? msm_plan((uint32_t)n, (uint32_t)nseg).extra : 1;
+  return (nq + nseg * X) * 72 * 4 * ML_EVENTS <= g.line_budget;
+}
+
 // ----- the verification pipeline on device pointers.
 // Sets [0, n) grouped in segments by seg_off (HOST array, nseg + 1 entries); per segment
 // a Miller partial (no final exponentiation) and an error flag.  rands == nullptr
@@ -798,6 +829,10 @@ void ml_tail(Ctx &c, hipStream_t st, const MlTables &mt, const uint32_t *T, uint
 //   side 2: signature group check, then S = sum r_i sig_i (waits for the keys' flags),
 //           then the lines of the (-g1, S) pairs (or of the MSM's weighted bucket sums)
 //   main:   hash_to_G2 -> the sets' lines;  join -> Miller product tree -> partials
+// With message groups (c.plan, GBLS_INIT_DEDUP: msgs holds the U unique messages) the pair space is
+// the U group pairs (sum of the members' r_i pk_i, H(m)) followed by the nseg X extra pairs: the
+// main stream hashes and takes lines over U messages, side 1 writes the per-set points to a
+// workspace of their own and sums them by group (k_g1s_msgsum), side 2 is per set as ever.
 bool pipeline_partials(Ctx &c, Device &d, const uint8_t *msgs, const uint32_t *msg_off,
                        const g2a *sigs, const PkSource &src, const uint64_t *rands,
                        bool sig_groupcheck, size_t n, const uint32_t *seg_off, size_t nseg,
@@ -825,11 +860,14 @@ bool pipeline_partials(Ctx &c, Device &d, const uint8_t *msgs, const uint32_t *m
     HIPCHK(hipStreamWaitEvent(own, c.ev_in, 0));
     st = own;
   }
+  const dedup::Plan *pl = c.plan;
+  c.plan = nullptr;
+  if (pl && (!rands || pl->n != n || pl->nseg != nseg)) return fail(GBLS_ERR_ARG);
+  const size_t nq = pl ? pl->ngroups : n;  // set-side Miller pairs = messages hashed
   bool single = !rands && n == nseg;  // one set per segment, r = 1
   for (size_t s = 0; single && s <= nseg; s++) single = seg_off[s] == s;
   // bucket MSM for S when every segment is large (segment sizes >= msm_min)
-  bool msm = rands && n > 0;
-  for (size_t s = 0; msm && s < nseg; s++) msm = seg_off[s + 1] - seg_off[s] >= g.msm_min;
+  const bool msm = msm_regime(rands != nullptr, n, seg_off, nseg);
   MsmPlan mp{};
   if (msm) {
     mp = msm_plan((uint32_t)n, (uint32_t)nseg);
@@ -838,7 +876,7 @@ bool pipeline_partials(Ctx &c, Device &d, const uint8_t *msgs, const uint32_t *m
   // extra Miller pairs per segment after the n sets: (-g1, S), or the MSM's weighted
   // bucket / window sums
   const size_t X = msm ? mp.extra : 1;
-  const size_t np = n + nseg * X;
+  const size_t np = nq + nseg * X;
   // ---- host tables, one staged upload:
   //   [pair list][groups][g2 chunks][seg_chunk][reduction levels][seg_off]
   // Level 0 of the Miller product: per segment, its pairs (sets, then the extra pairs)
@@ -852,6 +890,7 @@ bool pipeline_partials(Ctx &c, Device &d, const uint8_t *msgs, const uint32_t *m
   if (event_bytes * ML_EVENTS > g.line_budget)
     EC = (int)std::max<size_t>(1, g.line_budget / event_bytes);
   const bool sliced = EC < ML_EVENTS;
+  if (pl && sliced) return fail(GBLS_ERR_ARG);  // enqueue_host_batch drops the plan instead
   // Miller segments: the verification segments, or (grouped single checks, grp > 1) runs of
   // grp checks whose pairs (i, n + i) share one Miller product and one final exponentiation
   const bool grouped = grp > 1 && single && !sliced && grp_r;
@@ -868,6 +907,14 @@ bool pipeline_partials(Ctx &c, Device &d, const uint8_t *msgs, const uint32_t *m
           const uint32_t b = (uint32_t)(s * grp), e = (uint32_t)std::min(n, (s + 1) * grp);
           for (uint32_t i = b; i < e; i++) t.push_back(i);
           for (uint32_t i = b; i < e; i++) t.push_back((uint32_t)n + i);
+        });
+  else if (pl)  // per segment: its groups, then its extra pairs
+    mt = ml_tables(
+        tab, nseg, np, EC, d.nsimd, g.ml_rounds, g.ml_g,
+        [&](size_t s) { return pl->grp_seg_off[s + 1] - pl->grp_seg_off[s] + (uint32_t)X; },
+        [&](size_t s, std::vector<uint32_t> &t) {
+          for (uint32_t i = pl->grp_seg_off[s]; i < pl->grp_seg_off[s + 1]; i++) t.push_back(i);
+          for (size_t k = 0; k < X; k++) t.push_back((uint32_t)(nq + s * X + k));
         });
   else
     mt = ml_tables(
@@ -905,7 +952,8 @@ bool pipeline_partials(Ctx &c, Device &d, const uint8_t *msgs, const uint32_t *m
   if (sliced && !c.ensure(c.Ts, np * sizeof(g2h))) return false;
   if (sig_groupcheck && !c.ensure(c.pre2, n * sizeof(int32_t) + 16)) return false;
   if (grouped && !c.ensure(c.ng1, n * sizeof(g1a) + 16)) return false;
-  if (!c.ensure(c.U, 2 * n * sizeof(fp2) + 16) || !c.ensure(c.Q, 2 * n * sizeof(g2j) + 16) ||
+  if (pl && !c.ensure(c.Pset, n * sizeof(g1s) + 16)) return false;
+  if (!c.ensure(c.U, 2 * nq * sizeof(fp2) + 16) || !c.ensure(c.Q, 2 * nq * sizeof(g2j) + 16) ||
       !c.ensure(c.H, np * sizeof(g2a)) || !c.ensure(c.P, np * sizeof(g1s)) ||
       !c.ensure(c.R, 2 * n * sizeof(g2j) + 16) ||
       !c.ensure(c.gpart, nchunks * (sizeof(g2j) + 4)) || !c.ensure(c.lines, line_words * 4) ||
@@ -916,7 +964,9 @@ bool pipeline_partials(Ctx &c, Device &d, const uint8_t *msgs, const uint32_t *m
       !c.ensure(c.hparts, 4 * 64 * sizeof(fp12)))  // the split Horner's parts (<= 64 segments)
     return false;
   if (!c.upload_staged(c.tab, tab.data(), tab.size() * 4, st)) return false;
-  const uint32_t N = (uint32_t)n, NP = (uint32_t)np, NS = (uint32_t)nseg;
+  const uint32_t N = (uint32_t)n, NP = (uint32_t)np, NS = (uint32_t)nseg, NQ = (uint32_t)nq;
+  if (pl && trace_dedup())
+    fprintf(stderr, "gbls dedup: sets=%zu segments=%zu groups=%zu pairs=%zu\n", n, nseg, nq, np);
   // latency regime: each segment's S = sum r_i sig_i stays Jacobian (no inversion), its lines
   // taken projectively (k_lines_w4j)
   g2j *sj = nullptr;
@@ -937,11 +987,11 @@ bool pipeline_partials(Ctx &c, Device &d, const uint8_t *msgs, const uint32_t *m
   // main stream first: its first kernels reach the GPU before the side streams' floods
   {
     StageTimer t(S_H2C_FIELD, st);
-    launch_h2c_field(st, msgs, msg_off, N, nullptr, 0, c.U.as<fp2>());
+    launch_h2c_field(st, msgs, msg_off, NQ, nullptr, 0, c.U.as<fp2>());
   }
   {
     StageTimer t(S_H2C_MAP, st);
-    launch_h2c_map(st, c.U.as<fp2>(), 2 * N, c.Q.as<g2j>());
+    launch_h2c_map(st, c.U.as<fp2>(), 2 * NQ, c.Q.as<g2j>());
   }
   const g1a *pks = nullptr;
   const int32_t *pre = nullptr;
@@ -949,7 +999,12 @@ bool pipeline_partials(Ctx &c, Device &d, const uint8_t *msgs, const uint32_t *m
   HIPCHK(hipEventRecord(c.ev_pks, side1));
   {
     StageTimer t(S_G1MUL, side1);
-    launch_mv_g1mul(side1, pks, grouped ? grp_r : rands, N, c.P.as<g1s>());
+    launch_mv_g1mul(side1, pks, grouped ? grp_r : rands, N, pl ? c.Pset.as<g1s>() : c.P.as<g1s>());
+  }
+  if (pl) {  // each group's point: the sum of its members' r_i pk_i
+    StageTimer t(S_MSGSUM, side1);
+    const uint32_t *csr = c.in6.as<uint32_t>();
+    launch_g1s_msgsum(side1, c.Pset.as<g1s>(), csr, csr + NQ + 1, NQ, pl->max_group, c.P.as<g1s>());
   }
   const int32_t *pre2 = nullptr;
   if (c.sig_c) {  // MultiVerifier::finish's decompression, inside this submission
@@ -971,7 +1026,7 @@ bool pipeline_partials(Ctx &c, Device &d, const uint8_t *msgs, const uint32_t *m
     HIPCHK(hipStreamWaitEvent(side2, c.ev_pks, 0));
     StageTimer t(S_MSM, side2);
     launch_msm(side2, mp, c.msm.as<uint8_t>(), sigs, rands, pks, pre, pre2, N, T + segoff_at,
-               empty_is_error, c.H.as<g2a>(), c.P.as<g1s>(), seg_err);
+               empty_is_error, c.H.as<g2a>(), c.P.as<g1s>(), seg_err, NQ);
   } else if (!single) {
     StageTimer t(S_G2MUL, side2);
     launch_mv_g2mul(side2, sigs, rands, N, c.R.as<g2j>());
@@ -987,7 +1042,7 @@ bool pipeline_partials(Ctx &c, Device &d, const uint8_t *msgs, const uint32_t *m
     } else {  // the signature sums start at once; only their key flags wait for side 1
       launch_g2sum(side2, c.R.as<g2j>(), T + chunk_off, (uint32_t)nchunks, T + segchunk_off,
                    T + segoff_at, NS, N, pks, rands, pre, pre2, empty_is_error, gpart, gpart_err,
-                   c.P.as<g1s>(), c.H.as<g2a>(), seg_err, sj, c.ev_pks);
+                   c.P.as<g1s>(), c.H.as<g2a>(), seg_err, sj, c.ev_pks, NQ);
     }
   }
   // experiment (GBLS_LINES_S_MAIN): the MSM's extra pairs' lines on the main stream after the
@@ -995,22 +1050,22 @@ bool pipeline_partials(Ctx &c, Device &d, const uint8_t *msgs, const uint32_t *m
   const bool lines_s_main = msm && !sliced && g.lines_s_main;
   if (!lines_s_main) {  // the extra pairs' lines of the first event slice (all events when not sliced)
     StageTimer t(S_LINES_S, side2);
-    if (!sj || !launch_lines_jac(side2, sj, 1, N, NS, lc, c.lines.as<uint32_t>()))
-      launch_lines(side2, c.H.as<g2a>(), N, (uint32_t)(nseg * X), lc, 0, EC, c.Ts.as<g2h>(),
+    if (!sj || !launch_lines_jac(side2, sj, 1, NQ, NS, lc, c.lines.as<uint32_t>()))
+      launch_lines(side2, c.H.as<g2a>(), NQ, (uint32_t)(nseg * X), lc, 0, EC, c.Ts.as<g2h>(),
                    c.lines.as<uint32_t>(), g.lines_s_lane);
   }
   // latency regime: H(m) stays Jacobian (over Q[2 i]) and its lines take it projectively,
   // no inversion on the main chain
-  const bool jac_h = !sliced && N <= kW4Max;
+  const bool jac_h = !sliced && NQ <= kW4Max;
   {
     StageTimer t(S_H2C_CLEAR, st);
-    if (!jac_h || !launch_h2c_clear_jac(st, c.Q.as<g2j>(), N))
-      launch_h2c_clear(st, c.Q.as<g2j>(), N, c.H.as<g2a>());
+    if (!jac_h || !launch_h2c_clear_jac(st, c.Q.as<g2j>(), NQ))
+      launch_h2c_clear(st, c.Q.as<g2j>(), NQ, c.H.as<g2a>());
   }
   {  // the sets' lines of the first event slice, before the join
     StageTimer t(S_LINES, st);
-    if (!jac_h || !launch_lines_jac(st, c.Q.as<g2j>(), 2, 0, N, lc, c.lines.as<uint32_t>()))
-      launch_lines(st, c.H.as<g2a>(), 0, N, lc, 0, EC, c.Ts.as<g2h>(), c.lines.as<uint32_t>());
+    if (!jac_h || !launch_lines_jac(st, c.Q.as<g2j>(), 2, 0, NQ, lc, c.lines.as<uint32_t>()))
+      launch_lines(st, c.H.as<g2a>(), 0, NQ, lc, 0, EC, c.Ts.as<g2h>(), c.lines.as<uint32_t>());
   }
   HIPCHK(hipEventRecord(c.ev_side1, side1));
   HIPCHK(hipEventRecord(c.ev_side2, side2));
@@ -1018,7 +1073,7 @@ bool pipeline_partials(Ctx &c, Device &d, const uint8_t *msgs, const uint32_t *m
   HIPCHK(hipStreamWaitEvent(st, c.ev_side2, 0));
   if (lines_s_main) {
     StageTimer t(S_LINES_S, st);
-    launch_lines(st, c.H.as<g2a>(), N, (uint32_t)(nseg * X), lc, 0, EC, c.Ts.as<g2h>(), c.lines.as<uint32_t>(),
+    launch_lines(st, c.H.as<g2a>(), NQ, (uint32_t)(nseg * X), lc, 0, EC, c.Ts.as<g2h>(), c.lines.as<uint32_t>(),
                  g.lines_s_lane);
   }
   const uint32_t *Pc = nullptr;  // the points by line column (radix-2^28 Miller kernel)
@@ -1220,9 +1275,25 @@ bool enqueue_host_batch(Ctx &c, Device &d, const uint8_t *msgs, const g2a *sigs,
   size_t n = e - b;
   if (!c.begin(st)) return false;
   const bool single = rands == nullptr;
-  if (!c.upload_staged(c.in0, msgs + 32 * b, 32 * n, st) ||
-      (!single && !c.upload_staged(c.in3, rands + b, n * 8, st)))
+  // GBLS_INIT_DEDUP: this shard's sets grouped by message (per segment).  Without duplicates, or
+  // when the line buffer would be sliced (C5 scale), the plain path below runs unchanged.
+  dedup::Plan &plan = c.plan_host;
+  bool grouped_msgs = false;
+  if (!single && n > 1 && g.dedup.load(std::memory_order_relaxed)) {
+    dedup::build(plan, msgs + 32 * b, n, seg, nseg);
+    grouped_msgs = plan.has_duplicates() && lines_unsliced(plan.ngroups, n, seg, nseg);
+  }
+  if (grouped_msgs) {  // the unique messages in place of the n messages, and the groups' CSR
+    std::vector<uint32_t> &csr = c.host_tab;
+    csr.assign(plan.grp_off.begin(), plan.grp_off.end());
+    csr.insert(csr.end(), plan.grp_set.begin(), plan.grp_set.end());
+    if (!c.upload_staged(c.in0, plan.msgs.data(), plan.msgs.size(), st) ||
+        !c.upload_staged(c.in6, csr.data(), csr.size() * 4, st))
+      return false;
+  } else if (!c.upload_staged(c.in0, msgs + 32 * b, 32 * n, st)) {
     return false;
+  }
+  if (!single && !c.upload_staged(c.in3, rands + b, n * 8, st)) return false;
   const g2a *dsigs;
   if (sigs_c) {  // compressed: decompressed on the device by the pipeline (side stream 2)
     if (!c.upload_staged(c.in1, sigs_c + 96 * b, 96 * n, st) ||
@@ -1243,6 +1314,7 @@ bool enqueue_host_batch(Ctx &c, Device &d, const uint8_t *msgs, const g2a *sigs,
   }
   bool ok;
   const uint64_t *drands = single ? nullptr : c.in3.as<uint64_t>();
+  c.plan = grouped_msgs ? &plan : nullptr;
   if (verdicts)
     ok = c.ensure(c.out1, nseg * sizeof(int32_t)) &&
          pipeline_verdicts(c, d, c.in0.as<uint8_t>(), nullptr, dsigs, dsrc, drands, single, n, seg,
@@ -1251,8 +1323,9 @@ bool enqueue_host_batch(Ctx &c, Device &d, const uint8_t *msgs, const g2a *sigs,
     ok = c.ensure(c.part, sizeof(fp12)) && c.ensure(c.err, 16) &&
          pipeline_partials(c, d, c.in0.as<uint8_t>(), nullptr, dsigs, dsrc, drands, single, n, seg,
                            1, 0, c.part.as<fp12>(), c.err.as<int32_t>(), st);
-  c.sig_c = nullptr;  // the option is for this call only, consumed or not
+  c.sig_c = nullptr;  // the options are for this call only, consumed or not
   c.sig_st = nullptr;
+  c.plan = nullptr;
   if (!ok) return false;
   if (verdicts) {
     HIPCHK(hipMemcpyAsync(verdicts, c.out1.p, nseg * 4, hipMemcpyDeviceToHost, st));
@@ -1533,9 +1606,11 @@ int gbls_init(uint32_t device_mask, uint32_t flags) {
 
 uint32_t gbls_set_policy(uint32_t flags) {
   uint32_t prev = (g.coalesce.load() ? 0u : GBLS_INIT_NO_COALESCE) |
-                  (g.per_check.load() ? GBLS_INIT_PER_CHECK : 0u);
+                  (g.per_check.load() ? GBLS_INIT_PER_CHECK : 0u) |
+                  (g.dedup.load() ? GBLS_INIT_DEDUP : 0u);
   g.coalesce.store((flags & GBLS_INIT_NO_COALESCE) == 0);
   g.per_check.store((flags & GBLS_INIT_PER_CHECK) != 0);
+  g.dedup.store((flags & GBLS_INIT_DEDUP) != 0);
   return prev;
 }
 

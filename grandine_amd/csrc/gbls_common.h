@@ -58,6 +58,10 @@ extern uint32_t g_lane_r28;              // lane-regime clearing / lines in radi
 extern uint32_t g_clear_staged;          // lane clearing in five stages, chains at two waves per SIMD (GBLS_CLEAR_STAGED=1; off)
 extern uint32_t g_map_rows_max;          // hash_to_G2 maps of up to this many field elements on 16-lane rows (GBLS_MAP_ROWS_MAX)
 extern uint32_t g_lane_min;              // launches of at least this many points take the lane regime (GBLS_LANE_MIN)
+// k_g1s_msgsum: a launch whose largest message group has at least this many sets runs one wave
+// per group, smaller ones one lane per group (GBLS_MSGSUM_WAVE_MIN)
+constexpr uint32_t kMsgsumWaveMin = 8;
+extern uint32_t g_msgsum_wave_min;
 // line-coefficient buffer bound per submission (19.6 KB per pair: 4 GB = 214k pairs,
 // a C5 shard of 131 072 sets unsliced; tiny next to 288 GB of HBM): above it the Miller
 // lines are made in event slices (GBLS_LINE_BUDGET_MB overrides it)
@@ -101,11 +105,19 @@ void launch_mv_g2mul(hipStream_t st, const g2a *sigs, const uint64_t *rands, uin
 // chunks: 4 words per level-1 workgroup {segment, half, begin, end}; seg_chunk[nseg+1].
 // seg_err[s] = a set of s failed (infinite pk, zero scalar, pre[i] != 0) or, when
 // empty_is_error, s has no sets; an empty segment's partial is the identity otherwise.
+// xbase: the index of segment 0's extra pair in P / H (NONE: n, the pairs after the n sets;
+// with message groups the sets' pairs are the groups, fewer than n)
 void launch_g2sum(hipStream_t st, const g2j *R, const uint32_t *chunks, uint32_t nchunks,
                   const uint32_t *seg_chunk, const uint32_t *seg_off, uint32_t nseg, uint32_t n,
                   const g1a *pks, const uint64_t *rands, const int32_t *pre, const int32_t *pre2,
                   int empty_is_error, g2j *part, int32_t *part_err, g1s *P, g2a *H,
-                  int32_t *seg_err, g2j *Sj = nullptr, hipEvent_t keys_ready = nullptr);
+                  int32_t *seg_err, g2j *Sj = nullptr, hipEvent_t keys_ready = nullptr,
+                  uint32_t xbase = NONE);
+// Message groups (GBLS_INIT_DEDUP): P[g] = the sum of Pset[grp_set[j]] over grp_off[g] <= j <
+// grp_off[g + 1], groups [0, ngrp); an infinite sum is written all-zero.  max_group: the largest
+// group's size (picks the launch form, g_msgsum_wave_min)
+void launch_g1s_msgsum(hipStream_t st, const g1s *Pset, const uint32_t *grp_off, const uint32_t *grp_set,
+                       uint32_t ngrp, uint32_t max_group, g1s *P);
 // single checks (r = 1, one set per segment): the extra pair of segment s is (-g1, sig_s)
 // ng1_out: grouped single checks -- -g1 (affine) per check into ng1_out instead of the
 // pair's G1 point P[n + i], which the caller then scales by r_i (launch_mv_g1mul)
@@ -137,14 +149,14 @@ struct MsmPlan {
 // (profiles/r06/zz_ab_msm_min.txt), C2 / C1 unchanged (their segments are >= 4096 / < 2048)
 constexpr uint32_t kMsmMinPerSeg = 2048;
 MsmPlan msm_plan(uint32_t n, uint32_t nseg);
-// writes each segment's p.extra Miller pairs (P[n + s * extra + k] = a constant G1 weight,
-// H[...] = affine bucket or window sum), zeroes seg_err and flags empty segments when
-// empty_is_error
+// writes each segment's p.extra Miller pairs (P[xbase + s * extra + k] = a constant G1 weight,
+// H[...] = affine bucket or window sum; xbase = NONE: n), zeroes seg_err and flags empty segments
+// when empty_is_error
 // (pks, pre, pre2: the segment error flags of k_msm_count, as k_g2sum_final sets them)
 void launch_msm(hipStream_t st, const MsmPlan &p, uint8_t *ws, const g2a *sigs,
                 const uint64_t *rands, const g1a *pks, const int32_t *pre, const int32_t *pre2,
                 uint32_t n, const uint32_t *seg_off, int empty_is_error, g2a *H, g1s *P,
-                int32_t *seg_err);
+                int32_t *seg_err, uint32_t xbase = NONE);
 
 // k_lines.hip -- Miller-loop line functions of every pair
 // Where a pair's lines live: column col[pair] of ncol (col null: column = pair); word w of

@@ -442,7 +442,9 @@ MsmPlan msm_plan(uint32_t n, uint32_t nseg) {
 void launch_msm(hipStream_t st, const MsmPlan &p, uint8_t *ws, const g2a *sigs,
                 const uint64_t *rands, const g1a *pks, const int32_t *pre, const int32_t *pre2,
                 uint32_t n, const uint32_t *seg_off, int empty_is_error, g2a *H, g1s *P,
-                int32_t *seg_err) {
+                int32_t *seg_err, uint32_t xbase) {
+  // the pair kernels' `n` is only the index of the first extra pair
+  const uint32_t xb = xbase == NONE ? n : xbase;
   uint32_t *cnt = reinterpret_cast<uint32_t *>(ws + p.o_cnt);
   uint32_t *start = reinterpret_cast<uint32_t *>(ws + p.o_start);
   uint32_t *cur = reinterpret_cast<uint32_t *>(ws + p.o_cur);
@@ -474,10 +476,10 @@ void launch_msm(hipStream_t st, const MsmPlan &p, uint8_t *ws, const g2a *sigs,
   }
   if (!p.tree) {
     if (p.r28)
-      k_msm_pairs<true><<<nblk(p.nb), WG, 0, st>>>(chunk, cstart, p.nb, p.extra, n, seg_off,
+      k_msm_pairs<true><<<nblk(p.nb), WG, 0, st>>>(chunk, cstart, p.nb, p.extra, xb, seg_off,
                                                    empty_is_error, P, H, seg_err);
     else
-      k_msm_pairs<false><<<nblk(p.nb), WG, 0, st>>>(chunk, cstart, p.nb, p.extra, n, seg_off,
+      k_msm_pairs<false><<<nblk(p.nb), WG, 0, st>>>(chunk, cstart, p.nb, p.extra, xb, seg_off,
                                                     empty_is_error, P, H, seg_err);
     return;
   }
@@ -495,7 +497,7 @@ void launch_msm(hipStream_t st, const MsmPlan &p, uint8_t *ws, const g2a *sigs,
                                                          A[1 - src]);
     src = 1 - src;
   }
-  k_msm_wpairs<<<nblk(groups), WG, 0, st>>>(T[src], A[src], groups, (uint32_t)p.W, n, seg_off,
+  k_msm_wpairs<<<nblk(groups), WG, 0, st>>>(T[src], A[src], groups, (uint32_t)p.W, xb, seg_off,
                                             empty_is_error, P, H, seg_err);
 }
 

@@ -313,7 +313,9 @@ void launch_g2sum(hipStream_t st, const g2j *R, const uint32_t *chunks, uint32_t
                   const uint32_t *seg_chunk, const uint32_t *seg_off, uint32_t nseg, uint32_t n,
                   const g1a *pks, const uint64_t *rands, const int32_t *pre, const int32_t *pre2,
                   int empty_is_error, g2j *part, int32_t *part_err, g1s *P, g2a *H,
-                  int32_t *seg_err, g2j *Sj, hipEvent_t keys_ready) {
+                  int32_t *seg_err, g2j *Sj, hipEvent_t keys_ready, uint32_t xbase) {
+  // the final kernels' `n` is only the index of segment 0's extra pair
+  const uint32_t xb = xbase == NONE ? n : xbase;
   if (keys_ready) {  // level 1 before the keys, their flags after
     if (nchunks) k_g2sum_chunks<<<nchunks, WGR, 0, st>>>(R, chunks, n, nullptr, rands, nullptr, pre2, part, part_err);
     (void)hipStreamWaitEvent(st, keys_ready, 0);
@@ -323,10 +325,10 @@ void launch_g2sum(hipStream_t st, const g2j *R, const uint32_t *chunks, uint32_t
   }
 
   if (nseg && nseg <= kW4Max)
-    launch_g2sum_final_w4(st, part, part_err, chunks, seg_chunk, seg_off, nseg, n, empty_is_error, P, H, seg_err,
+    launch_g2sum_final_w4(st, part, part_err, chunks, seg_chunk, seg_off, nseg, xb, empty_is_error, P, H, seg_err,
                           Sj);
   else if (nseg)
-    k_g2sum_final<<<nseg, WG, 0, st>>>(part, part_err, chunks, seg_chunk, seg_off, nseg, n,
+    k_g2sum_final<<<nseg, WG, 0, st>>>(part, part_err, chunks, seg_chunk, seg_off, nseg, xb,
                                        empty_is_error, P, H, seg_err);
 }
 

@@ -115,20 +115,33 @@ enum {
  * cross-caller coalescing of concurrent host-pointer multi_verify calls (f3).
  * GBLS_INIT_TUNING (tests and benchmark sweeps only) lets gbls_init read the engine's
  * tuning environment variables (GBLS_MSM_MIN, GBLS_LINE_BUDGET_MB, GBLS_ML_G,
- * GBLS_ML_ROUNDS, GBLS_PRIO_MODE, GBLS_SIDE2_HIGH, GBLS_ROW_CLEAR_MAX); without it the
+ * GBLS_ML_ROUNDS, GBLS_PRIO_MODE, GBLS_SIDE2_HIGH, GBLS_ROW_CLEAR_MAX,
+ * GBLS_MSGSUM_WAVE_MIN); without it the
  * measured defaults are fixed and no environment variable changes the engine.
  * GBLS_INIT_PER_CHECK: batches of independent checks get one Miller product and final
  * exponentiation per check (deterministic, as the reference's fast_aggregate_verify) instead
  * of the grouped form described at gbls_fast_aggregate_verify_batch.
- * The policy flags (GBLS_INIT_NO_COALESCE, GBLS_INIT_PER_CHECK) are sticky: a gbls_init call
- * that names one turns it on, also on an engine that is already open, and no gbls_init call
- * turns it off (a library's lazy gbls_init(mask, 0) cannot undo a harness's PER_CHECK).  The
- * other bits apply on the first call only.  gbls_set_policy sets both policies outright
- * (flags & (GBLS_INIT_NO_COALESCE | GBLS_INIT_PER_CHECK), the rest ignored) and returns the
- * previous policy bits; it needs no device. */
+ * GBLS_INIT_DEDUP (off by default): batch verification groups the sets of a segment that carry
+ * the same 32-byte message and pays one hash_to_G2, one set of Miller lines and one Miller pair
+ * per distinct message, e(sum_i r_i pk_i, H(m)) over the group's sets; the random scalars stay
+ * per set on both sides, so every verdict, per-set rejection and signature status is what it is
+ * without the flag.  It applies to the host-pointer entry points that take random scalars
+ * (gbls_multi_verify, _segments, _indexed, _compressed, _compressed_ex, _bisect) and to what the
+ * coalescer merges out of them; not to the _device entry points (their messages are already in
+ * device memory) and not to single checks (rands == NULL).  A batch without duplicates runs
+ * exactly as without the flag, and so does one so large that its Miller lines are made in
+ * event slices (above the line-buffer bound, C5 scale).  GBLS_TRACE_DEDUP=1 in the environment
+ * prints one line per grouped submission to stderr.
+ * The policy flags (GBLS_INIT_NO_COALESCE, GBLS_INIT_PER_CHECK, GBLS_INIT_DEDUP) are sticky: a
+ * gbls_init call that names one turns it on, also on an engine that is already open, and no
+ * gbls_init call turns it off (a library's lazy gbls_init(mask, 0) cannot undo a harness's
+ * PER_CHECK).  The other bits apply on the first call only.  gbls_set_policy sets the three
+ * policies outright (flags & (GBLS_INIT_NO_COALESCE | GBLS_INIT_PER_CHECK | GBLS_INIT_DEDUP), the
+ * rest ignored) and returns the previous policy bits; it needs no device. */
 #define GBLS_INIT_NO_COALESCE 0x100u
 #define GBLS_INIT_TUNING 0x200u
 #define GBLS_INIT_PER_CHECK 0x400u
+#define GBLS_INIT_DEDUP 0x800u
 int gbls_init(uint32_t device_mask, uint32_t flags);
 uint32_t gbls_set_policy(uint32_t flags);
 int gbls_last_error(void);

@@ -32,6 +32,8 @@ use blst::{
 };
 
 pub use ffi::{gbls_p1_affine as P1, gbls_p2_affine as P2};
+// the policy bits of [`set_policy`]
+pub use ffi::{GBLS_INIT_DEDUP, GBLS_INIT_NO_COALESCE, GBLS_INIT_PER_CHECK};
 
 // the engine's 64-bit limbs are blst's limb_t on every target Grandine builds for
 const _: () = assert!(core::mem::size_of::<blst::limb_t>() == 8);
@@ -128,8 +130,10 @@ static ENGINE: OnceLock<EngineResult<usize>> = OnceLock::new();
 /// result is cached: a node without a usable GPU pays for the probe once and then takes the
 /// CPU path on every call without touching the library again.  `GBLS_PER_CHECK=1` asks for
 /// deterministic per-check verdicts (`GBLS_INIT_PER_CHECK`, e.g. spec-test runs) and
-/// `GBLS_NO_COALESCE=1` turns cross-caller coalescing off; both are sticky in the library, so
-/// no later initialisation clears them (see also [`set_policy`]).
+/// `GBLS_NO_COALESCE=1` turns cross-caller coalescing off; `GBLS_DEDUP=1` groups the sets of a
+/// batch by message (`GBLS_INIT_DEDUP`: one hash and one pairing per distinct message, verdicts
+/// unchanged).  All three are sticky in the library, so no later initialisation clears them
+/// (see also [`set_policy`]).
 pub fn engine() -> EngineResult<usize> {
     *ENGINE.get_or_init(|| {
         let mask = std::env::var("GBLS_DEVICE_MASK")
@@ -148,6 +152,9 @@ pub fn engine() -> EngineResult<usize> {
         if on("GBLS_NO_COALESCE") {
             flags |= ffi::GBLS_INIT_NO_COALESCE;
         }
+        if on("GBLS_DEDUP") {
+            flags |= ffi::GBLS_INIT_DEDUP;
+        }
         // SAFETY: plain integers in; the library serialises its own initialisation.
         let rc = unsafe { ffi::gbls_init(mask, flags) };
         status(rc)?;
@@ -157,8 +164,8 @@ pub fn engine() -> EngineResult<usize> {
     })
 }
 
-/// Sets the engine's policies outright (`GBLS_INIT_PER_CHECK`, `GBLS_INIT_NO_COALESCE`; other
-/// bits ignored) and returns the previous ones.  Needs no device.
+/// Sets the engine's policies outright (`GBLS_INIT_PER_CHECK`, `GBLS_INIT_NO_COALESCE`,
+/// `GBLS_INIT_DEDUP`; other bits ignored) and returns the previous ones.  Needs no device.
 pub fn set_policy(flags: u32) -> u32 {
     // SAFETY: a plain integer in and out.
     unsafe { ffi::gbls_set_policy(flags) }
