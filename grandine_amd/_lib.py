@@ -51,6 +51,7 @@ PK_IS_INFINITY = 6
 BAD_SCALAR = 7
 ERR_NO_DEVICE = 100
 CALL_BLOCK = 0x1  # gbls_multi_verify_compressed_ex: block-import priority class
+NO_COMMITTEE = 0xFFFFFFFF  # include/grandine_bls_gpu_committees.h: a set that names no committee
 
 P1_BYTES = 96
 P2_BYTES = 192
@@ -100,6 +101,14 @@ EXPORTS = [
     "gbls_profile_read",
     "gbls_profile_reset",
     "gbls_stage_name",
+]
+# include/grandine_bls_gpu_committees.h (cached committee key sums)
+EXPORTS_COMMITTEES = [
+    "gbls_committees_set",
+    "gbls_committees_size",
+    "gbls_committees_clear",
+    "gbls_g1_aggregate_committees",
+    "gbls_multi_verify_committees",
 ]
 
 
@@ -187,6 +196,12 @@ def load_library():
                 "gbls_profile_read": (_c.c_int, [_vp, _vp, _c.c_int]),
                 "gbls_profile_reset": (None, []),
                 "gbls_stage_name": (_c.c_char_p, [_c.c_int]),
+                "gbls_committees_set": (_c.c_int, [_sz, _vp, _vp, _sz, _vp]),
+                "gbls_committees_size": (_sz, []),
+                "gbls_committees_clear": (_c.c_int, []),
+                "gbls_g1_aggregate_committees": (_c.c_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
+                "gbls_multi_verify_committees": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp,
+                                                            _c.c_uint32]),
             }
             for name, (res, args) in sig.items():
                 fn = getattr(lib, name)

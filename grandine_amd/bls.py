@@ -316,6 +316,36 @@ class Signature:
             G.u64_array(randoms), n, st, call_flags)
 
     @staticmethod
+    def multi_verify_compressed_committees(messages: Iterable[bytes], signature_bytes: Iterable[bytes],
+                                           committee_slots: Iterable[int],
+                                           validator_indices: Iterable[Sequence[int]],
+                                           randoms: Sequence[int] = None, call_flags: int = 0) -> int:
+        """multi_verify_compressed_indexed over cached committee sums
+        (gbls_multi_verify_committees): set i's key is committee slot ``committee_slots[i]`` MINUS
+        the registry keys ``validator_indices[i]`` (its absent members), or, when the slot is
+        ``None``, the plain sum of those keys.  Returns as multi_verify_compressed."""
+        msgs = [bytes(m) for m in messages]
+        sigs = [bytes(s) for s in signature_bytes]
+        com = [G.NO_COMMITTEE if c is None else int(c) for c in committee_slots]
+        idx = [list(v) for v in validator_indices]
+        n = len(sigs)
+        if n == 0 or len(msgs) != n or len(idx) != n or len(com) != n:
+            return G.VERIFY_FAIL
+        if any(len(m) != 32 for m in msgs) or any(len(s) != 96 for s in sigs):
+            raise ValueError("messages must be 32-byte signing roots and signatures 96 bytes")
+        if randoms is None:
+            randoms = [secrets.randbits(64) or 1 for _ in range(n)]
+        off = [0]
+        for v in idx:
+            off.append(off[-1] + len(v))
+        flat = [i for v in idx for i in v]
+        L = G.lib()
+        st = G.i32_array(n)
+        return L.gbls_multi_verify_committees(
+            G.buf(b"".join(msgs)), G.buf(b"".join(sigs)), G.u32_array(com), G.u32_array(flat or [0]),
+            G.u32_array(off), G.u64_array(randoms), n, st, call_flags)
+
+    @staticmethod
     def verify_batch_compressed(messages: Iterable[bytes], signature_bytes: Iterable[bytes],
                                 public_keys: Iterable) -> List:
         """SingleVerifier::extend's try_from + verify per triple (verifier.rs:215-236) as ONE
@@ -447,3 +477,51 @@ class Registry:
     def forget(cls) -> None:
         """Tests: the process's engine registry was overwritten by someone else."""
         cls._mirrored = 0
+        Committees.forget()  # cached sums are snapshots of the overwritten keys
+
+
+class Committees:
+    """The engine's cached committee key sums (include/grandine_bls_gpu_committees.h): slot s holds
+    the sum of one committee's registry keys, loaded once per epoch (the sync committee once per
+    period), so that a set's key is the slot minus its few ABSENT members.  The mirror remembers
+    each loaded slot's member list; ``covers`` says whether a triple may name the slot."""
+
+    _members = {}  # slot -> tuple of validator indices, for slots loaded with status SUCCESS
+
+    @classmethod
+    def set(cls, first: int, committees: Sequence[Sequence[int]]) -> List[int]:
+        """gbls_committees_set: committees[c] (validator indices) into slot first + c.  Returns
+        the per-committee statuses; only SUCCESS slots are remembered (the others are invalid)."""
+        coms = [[int(i) for i in c] for c in committees]
+        off = [0]
+        for c in coms:
+            off.append(off[-1] + len(c))
+        L = G.lib()
+        st = G.i32_array(len(coms))
+        for c in range(len(coms)):
+            cls._members.pop(first + c, None)
+        G.check(L.gbls_committees_set(first, G.u32_array([i for c in coms for i in c] or [0]), G.u32_array(off),
+                                      len(coms), st), "gbls_committees_set")
+        for c, members in enumerate(coms):
+            if st[c] == G.SUCCESS:
+                cls._members[first + c] = tuple(members)
+        return [st[c] for c in range(len(coms))]
+
+    @classmethod
+    def size(cls) -> int:
+        return int(G.lib().gbls_committees_size())
+
+    @classmethod
+    def clear(cls) -> None:
+        cls._members = {}
+        G.check(G.lib().gbls_committees_clear(), "gbls_committees_clear")
+
+    @classmethod
+    def covers(cls, slot: int, members: Iterable[int]) -> bool:
+        """True when ``slot`` was loaded with exactly this member list."""
+        return slot is not None and cls._members.get(int(slot)) == tuple(int(i) for i in members)
+
+    @classmethod
+    def forget(cls) -> None:
+        """Tests: the process's engine table was cleared or overwritten by someone else."""
+        cls._members = {}

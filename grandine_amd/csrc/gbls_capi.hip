@@ -34,7 +34,9 @@
 #include <vector>
 
 #include "../../include/grandine_bls_gpu.h"
+#include "../../include/grandine_bls_gpu_committees.h"
 #include "gbls_common.h"
+#include "gbls_committees.h"
 #include "gbls_dedup.h"
 #include "gbls_sched.h"
 #include "gbls_tables.h"
@@ -60,6 +62,7 @@ uint32_t gbls::g_lane_min = gbls::kLaneRegimeSets;
 uint32_t gbls::g_clear_staged = 0;
 uint32_t gbls::g_map_rows_max = 2048;
 uint32_t gbls::g_msgsum_wave_min = gbls::kMsgsumWaveMin;
+uint32_t gbls::g_committee_row_min = gbls::kCommitteeRowMin;
 
 namespace {
 
@@ -243,7 +246,7 @@ struct Ctx {
   bool used = false;                  // last_stream is meaningful
   hipStream_t last_stream = nullptr;  // main stream of the previous call
   Buf in0, in1, in2, in3, in4, in5, U, Q, H, P, Pc, R, Sj, gpart, lines, Ts, V0, V1, V28, hparts, tab, part, err, out0,
-      out1, pks, pre, pre2, msm, sigd, sigst, rnd, ng1, gerr, gv, redo, rtab, in6, Pset;
+      out1, pks, pre, pre2, msm, sigd, sigst, rnd, ng1, gerr, gv, redo, rtab, in6, Pset, in7;
   // per-call option of the next pipeline_partials on this lease: compressed signatures
   // (96 B each, device) to decompress on the signature-side stream into `sigs`, with their
   // BLST_ERROR statuses (device) failing their segments (consumed and reset by the pipeline)
@@ -486,6 +489,11 @@ struct Device {
   hipStream_t reg_st = nullptr, retire_st = nullptr;
   hipEvent_t reg_ev = nullptr, reg_tmp = nullptr;
   bool reg_ev_set = false;
+  // committee table (replica): slot c = the sum of one committee's registry keys, all-zero when
+  // invalid.  Guarded, written, grown and retired exactly as the registry (reg_mu, reg_st,
+  // reg_ev, the readers' Ctx::ev_reg); each device sums its slots from its own registry replica.
+  Buf com;
+  bool com_pooled = false;
 };
 
 struct Engine {
@@ -495,6 +503,7 @@ struct Engine {
   std::atomic<uint32_t> rr{0};
   std::shared_mutex reg_mu;
   size_t reg_n = 0;
+  size_t com_n = 0;  // committee table slots (guarded by reg_mu)
   std::atomic<bool> coalesce{true};
   std::atomic<bool> per_check{false};  // GBLS_INIT_PER_CHECK: no grouped single checks
   std::atomic<bool> dedup{false};      // GBLS_INIT_DEDUP: host batches grouped by message
@@ -605,6 +614,8 @@ bool engine_init(uint32_t device_mask, uint32_t flags) {
     if (const char *e = std::getenv("GBLS_MAP_ROWS_MAX")) g_map_rows_max = (uint32_t)std::strtoul(e, nullptr, 10);
     if (const char *e = std::getenv("GBLS_MSGSUM_WAVE_MIN"))
       g_msgsum_wave_min = std::max(1u, (uint32_t)std::strtoul(e, nullptr, 10));
+    if (const char *e = std::getenv("GBLS_COMMITTEE_ROW_MIN"))
+      g_committee_row_min = std::max(1u, (uint32_t)std::strtoul(e, nullptr, 10));
     if (const char *e = std::getenv("GBLS_LANE_MIN")) g_lane_min = std::max(1u, (uint32_t)std::strtoul(e, nullptr, 10));
     if (const char *e = std::getenv("GBLS_CU_SPLIT_MAX"))
       g.cu_split_max = (uint32_t)std::strtoul(e, nullptr, 10);
@@ -766,11 +777,16 @@ bool resolve_pks(Ctx &c, Device &d, const PkSource &src, size_t n, hipStream_t s
     return true;
   }
   if (!src.pts && !src.idx) return fail(GBLS_ERR_ARG);
+  if (src.com && !(src.idx && src.off)) return fail(GBLS_ERR_ARG);
   if (!c.ensure(c.pks, n * sizeof(g1a)) || !c.ensure(c.pre, n * sizeof(int32_t))) return false;
   StageTimer t(S_PK_GATHER, st);
   const g1a *reg = d.reg.as<g1a>();
   if (src.idx && !registry_read_begin(c, d, st)) return false;
-  if (src.pts)
+  if (src.com)  // cached committee sums minus the listed keys (the table is read as the registry is)
+    launch_g1_committee_keys(st, reg, (uint32_t)g.reg_n, d.com.as<g1a>(), (uint32_t)g.com_n, src.com,
+                             src.idx, src.off, (uint32_t)n, src.max_len, c.pks.as<g1a>(),
+                             c.pre.as<int32_t>());
+  else if (src.pts)
     launch_g1_aggregate_seg(st, src.pts, src.off, (uint32_t)n, c.pks.as<g1a>(),
                             c.pre.as<int32_t>());
   else if (src.off)
@@ -1236,7 +1252,20 @@ bool pipeline_verdicts(Ctx &c, Device &d, const uint8_t *msgs, const uint32_t *m
 bool upload_pks(Ctx &c, const PkSource &host, size_t b, size_t e, hipStream_t st, PkSource *dev) {
   size_t n = e - b;
   *dev = PkSource();
-  if (host.off) {
+  if (host.com) {  // committee slots per set, with index ranges (possibly all empty)
+    if (!host.off) return fail(GBLS_ERR_ARG);
+    uint32_t base = host.off[b], cnt = host.off[e] - base;
+    std::vector<uint32_t> off(n + 1);
+    for (size_t i = 0; i <= n; i++) off[i] = host.off[b + i] - base;
+    for (size_t i = 0; i < n; i++) dev->max_len = std::max(dev->max_len, off[i + 1] - off[i]);
+    if (!c.upload_staged(c.in5, off.data(), (n + 1) * 4, st) ||
+        !c.upload_staged(c.in2, cnt ? host.idx + base : nullptr, (size_t)cnt * 4, st) ||
+        !c.upload_staged(c.in7, host.com + b, n * 4, st))
+      return false;
+    dev->off = c.in5.as<uint32_t>();
+    dev->idx = c.in2.as<uint32_t>();
+    dev->com = c.in7.as<uint32_t>();
+  } else if (host.off) {
     uint32_t base = host.off[b], cnt = host.off[e] - base;
     std::vector<uint32_t> off(n + 1);
     for (size_t i = 0; i <= n; i++) off[i] = host.off[b + i] - base;
@@ -1542,7 +1571,8 @@ bool registry_streams(Device &d) {
 // loaded entries, the loaded ones copied), and the old one freed on d.retire_st once the copy
 // and every kernel that read it have run (each context's last registry read, and the replica
 // copies of earlier updates).  No host wait, no device synchronisation.
-bool registry_grow(Device &d, size_t need, size_t loaded) {
+// `tab` is the registry (d.reg) or the committee table (d.com), `tab_pooled` its allocation kind.
+bool table_grow(Device &d, Buf &tab, bool &tab_pooled, size_t need, size_t loaded) {
   const size_t want = need + need / 4;
   void *nb = nullptr;
   bool pooled = true;
@@ -1551,7 +1581,7 @@ bool registry_grow(Device &d, size_t need, size_t loaded) {
     pooled = false;
     HIPCHK(hipMalloc(&nb, want));
   }
-  if (loaded) HIPCHK(hipMemcpyAsync(nb, d.reg.p, loaded, hipMemcpyDeviceToDevice, d.reg_st));
+  if (loaded) HIPCHK(hipMemcpyAsync(nb, tab.p, loaded, hipMemcpyDeviceToDevice, d.reg_st));
   HIPCHK(hipMemsetAsync(static_cast<uint8_t *>(nb) + loaded, 0, want - loaded, d.reg_st));
   // kept tables of earlier growths (no stream-ordered allocator) whose readers have finished
   for (size_t i = 0; i < d.reg_kept.size();) {
@@ -1564,7 +1594,7 @@ bool registry_grow(Device &d, size_t need, size_t loaded) {
     }
   }
   (void)hipGetLastError();
-  if (d.reg.p) {
+  if (tab.p) {
     // the retire stream is created by the first growth that retires a table (a stream holds a
     // hardware queue from its creation; the engine's queue set is tuned, see kPrewarmCtx)
     if (!d.retire_st) HIPCHK(hipStreamCreateWithFlags(&d.retire_st, hipStreamNonBlocking));
@@ -1577,20 +1607,42 @@ bool registry_grow(Device &d, size_t need, size_t loaded) {
     for (auto &o : g.devs)  // replica copies of earlier updates read device 0's table
       if (o->reg_ev_set && hipStreamWaitEvent(d.retire_st, o->reg_ev, 0) != hipSuccess) ok = false;
     if (!ok) return fail(GBLS_ERR_HIP);
-    if (d.reg_pooled) {
-      HIPCHK(hipFreeAsync(d.reg.p, d.retire_st));
+    if (tab_pooled) {
+      HIPCHK(hipFreeAsync(tab.p, d.retire_st));
     } else {  // readers may still be running: kept behind an event, never host-waited
-      Device::Kept k{d.reg.p, nullptr};
+      Device::Kept k{tab.p, nullptr};
       HIPCHK(hipEventCreateWithFlags(&k.ev, hipEventDisableTiming));
       HIPCHK(hipEventRecord(k.ev, d.retire_st));
       d.reg_kept.push_back(k);
     }
   }
-  d.reg.p = nb;
-  d.reg.cap = want;
-  d.reg_pooled = pooled;
+  tab.p = nb;
+  tab.cap = want;
+  tab_pooled = pooled;
   return true;
 }
+bool registry_grow(Device &d, size_t need, size_t loaded) {
+  return table_grow(d, d.reg, d.reg_pooled, need, loaded);
+}
+// a kernel is about to overwrite loaded slots of a table of d in place (on d.reg_st): after every
+// kernel still reading them (each context's last registry / committee read)
+bool table_wait_readers(Device &d) {
+  bool ok = true;
+  d.pool.for_each([&](Ctx &c) {
+    if (c.reg_read && hipStreamWaitEvent(d.reg_st, c.ev_reg, 0) != hipSuccess) ok = false;
+  });
+  return ok || fail(GBLS_ERR_HIP);
+}
+// a block import in progress: normal submissions keep off the reserved CUs meanwhile
+struct BlockActive {
+  bool on;
+  explicit BlockActive(bool b) : on(b) {
+    if (on) g.block_active.fetch_add(1);
+  }
+  ~BlockActive() {
+    if (on && g.block_active.fetch_sub(1) == 1) co.wake();  // held normal callers go on
+  }
+};
 }  // namespace
 
 #define API_BEGIN                   \
@@ -1995,15 +2047,7 @@ int gbls_multi_verify_compressed_ex(const uint8_t (*msgs)[32], const uint8_t (*s
   r.sigs_c = &sigs[0][0];
   r.sig_status = sig_status;
   r.prio = (call_flags & GBLS_CALL_BLOCK) ? 1 : 0;
-  struct BlockActive {  // normal submissions keep off the reserved CUs meanwhile
-    bool on;
-    explicit BlockActive(bool b) : on(b) {
-      if (on) g.block_active.fetch_add(1);
-    }
-    ~BlockActive() {
-      if (on && g.block_active.fetch_sub(1) == 1) co.wake();  // held normal callers go on
-    }
-  } block_active(r.prio != 0);
+  BlockActive block_active(r.prio != 0);
   if (!coalesced_verify(r)) {
     fill(sig_status, n, GBLS_BAD_ENCODING);
     return GBLS_VERIFY_FAIL;
@@ -2188,6 +2232,8 @@ int gbls_registry_set(size_t first, const uint8_t (*pks)[48], size_t n, int32_t 
   };
   std::unique_lock<std::shared_mutex> wl(g.reg_mu);
   {
+    // loaded keys are rewritten: the cached committee sums are snapshots of them, all dropped
+    if (first < g.reg_n) g.com_n = 0;
     new_n = std::max(g.reg_n, first + n);
     if (new_n > 0xffffffffull) return fail(GBLS_ERR_ARG), FAILED;
     Device &d0 = *g.devs[0];
@@ -2263,6 +2309,165 @@ int gbls_registry_set(size_t first, const uint8_t (*pks)[48], size_t n, int32_t 
 size_t gbls_registry_size(void) {
   std::shared_lock<std::shared_mutex> rl(g.reg_mu);
   return g.reg_n;
+}
+
+// ---- cached committee key sums (include/grandine_bls_gpu_committees.h).  The table lives beside
+// the registry under the same discipline: written under the exclusive registry lock on each
+// device's registry stream (so behind every earlier registry write), followed by reg_ev for later
+// readers, grown and retired by table_grow behind the readers' events.  Every device sums the
+// committees from ITS OWN registry replica (launch_g1_aggregate_idx writing at the slot offset):
+// the devices work side by side, so n devices cost the wall time of one, with no peer copy and no
+// cross-device event; the index lists (4 bytes per member) are uploaded once per device.
+int gbls_committees_set(size_t first, const uint32_t *idx, const uint32_t *off, size_t ncom,
+                        int32_t *status) {
+  fill(status, ncom, GBLS_BAD_ENCODING);
+  API_BEGIN
+  if (first > kMaxCommittees || ncom > kMaxCommittees - first) return fail(GBLS_ERR_ARG), FAILED;
+  if (ncom && !valid_offsets(off, ncom, off ? off[ncom] : 0)) return fail(GBLS_ERR_ARG), FAILED;
+  const size_t nidx = ncom ? off[ncom] : 0;
+  if (nidx && !idx) return fail(GBLS_ERR_ARG), FAILED;
+  std::vector<int32_t> st0(ncom);
+  std::vector<hipEvent_t> done;
+  struct EvGuard {
+    std::vector<hipEvent_t> &v;
+    ~EvGuard() {
+      for (hipEvent_t e : v) (void)hipEventDestroy(e);
+    }
+  } guard{done};
+  size_t new_n = 0;  // the size this call commits
+  // a failure truncates the table to `first` (after the lock was released only while no later
+  // call has moved the size on from this call's)
+  auto broken = [&](std::unique_lock<std::shared_mutex> &wl) {
+    const bool relock = !wl.owns_lock();
+    if (relock) wl.lock();
+    if (!relock || g.com_n == new_n) g.com_n = std::min(g.com_n, first);
+    fill(status, ncom, GBLS_BAD_ENCODING);
+    return FAILED;
+  };
+  std::unique_lock<std::shared_mutex> wl(g.reg_mu);
+  new_n = std::max(g.com_n, first + ncom);
+  for (auto &dp : g.devs) {
+    Device &d = *dp;
+    if (!registry_streams(d) || hipSetDevice(d.hipdev) != hipSuccess) return fail(GBLS_ERR_HIP), broken(wl);
+    if (new_n * sizeof(g1a) > d.com.cap) {
+      if (!table_grow(d, d.com, d.com_pooled, new_n * sizeof(g1a), g.com_n * sizeof(g1a))) return broken(wl);
+    } else {
+      // written in place: behind every kernel that may still read the slots (also those of a
+      // table cleared meanwhile), so no reader sees a half-written sum
+      if (!table_wait_readers(d)) return broken(wl);
+      if (first > g.com_n &&  // a gap past the loaded slots: never-written slots are zero
+          hipMemsetAsync(d.com.as<g1a>() + g.com_n, 0, (first - g.com_n) * sizeof(g1a), d.reg_st) != hipSuccess)
+        return fail(GBLS_ERR_HIP), broken(wl);
+    }
+    if (ncom) {
+      Lease L(d);  // workspaces and staging; the work itself runs on the registry stream
+      Ctx &c = *L;
+      hipStream_t st = d.reg_st;
+      if (!L.ok() || !c.begin(st) || !c.upload_staged(c.in0, idx, nidx * 4, st) ||
+          !c.upload_staged(c.in1, off, (ncom + 1) * 4, st) || !c.ensure(c.out1, ncom * sizeof(int32_t)))
+        return broken(wl);
+      launch_g1_aggregate_idx(st, d.reg.as<g1a>(), (uint32_t)g.reg_n, c.in0.as<uint32_t>(),
+                              c.in1.as<uint32_t>(), (uint32_t)ncom, d.com.as<g1a>() + first,
+                              c.out1.as<int32_t>());
+      if (&d == g.devs[0].get() &&  // the statuses are the same on every replica
+          hipMemcpyAsync(st0.data(), c.out1.p, ncom * 4, hipMemcpyDeviceToHost, st) != hipSuccess)
+        return fail(GBLS_ERR_HIP), broken(wl);
+    }
+    // later readers wait (on the GPU) for this update; this call waits on its own events
+    hipEvent_t e = nullptr;
+    if (hipEventRecord(d.reg_ev, d.reg_st) != hipSuccess ||
+        hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess)
+      return fail(GBLS_ERR_HIP), broken(wl);
+    done.push_back(e);
+    if (hipEventRecord(e, d.reg_st) != hipSuccess) return fail(GBLS_ERR_HIP), broken(wl);
+    d.reg_ev_set = true;
+  }
+  g.com_n = new_n;
+  wl.unlock();
+  for (hipEvent_t e : done)
+    if (hipEventSynchronize(e) != hipSuccess) return fail(GBLS_ERR_HIP), broken(wl);
+  if (ncom) std::memcpy(status, st0.data(), ncom * 4);
+  return GBLS_SUCCESS;
+}
+
+size_t gbls_committees_size(void) {
+  std::shared_lock<std::shared_mutex> rl(g.reg_mu);
+  return g.com_n;
+}
+
+int gbls_committees_clear(void) {
+  API_BEGIN
+  std::unique_lock<std::shared_mutex> wl(g.reg_mu);
+  g.com_n = 0;
+  return GBLS_SUCCESS;
+}
+
+// the arguments of a committee key source (both calls below)
+static bool committee_args_ok(const uint32_t *com, const uint32_t *pk_idx, const uint32_t *pk_off, size_t n) {
+  if (!com || !pk_off || n > 0xfffffffeull || !valid_offsets(pk_off, n, pk_off[n])) return false;
+  return pk_idx || pk_off[n] == 0;
+}
+
+int gbls_g1_aggregate_committees(const uint32_t *com, const uint32_t *pk_idx, const uint32_t *pk_off,
+                                 size_t n, gbls_p1_affine *out, int32_t *status) {
+  fill(status, n, GBLS_BAD_ENCODING);
+  if (out) std::memset(out, 0, n * sizeof(*out));
+  API_BEGIN
+  if (n == 0) return GBLS_SUCCESS;
+  if (!out || !committee_args_ok(com, pk_idx, pk_off, n)) return fail(GBLS_ERR_ARG), FAILED;
+  PkSource src, dsrc;
+  src.com = com;
+  src.idx = pk_idx;
+  src.off = pk_off;
+  std::shared_lock<std::shared_mutex> rl(g.reg_mu);
+  Device &d = pick_device();
+  Lease L(d);
+  Ctx &c = *L;
+  hipStream_t st = c.own;
+  const g1a *keys = nullptr;
+  const int32_t *pre = nullptr;
+  if (!L.ok() || !c.begin(st) || !upload_pks(c, src, 0, n, st, &dsrc) ||
+      !resolve_pks(c, d, dsrc, n, st, &keys, &pre))
+    return FAILED;
+  if (hipMemcpyAsync(out, keys, n * sizeof(g1a), hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipMemcpyAsync(status, pre, n * 4, hipMemcpyDeviceToHost, st) != hipSuccess)
+    return fail(GBLS_ERR_HIP), FAILED;
+  rl.unlock();  // enqueued: the host wait below does not hold up registry updates
+  if (hipStreamSynchronize(st) != hipSuccess) {
+    fill(status, n, GBLS_BAD_ENCODING);
+    std::memset(out, 0, n * sizeof(*out));
+    return fail(GBLS_ERR_HIP), FAILED;
+  }
+  return GBLS_SUCCESS;
+}
+
+int gbls_multi_verify_committees(const uint8_t (*msgs)[32], const uint8_t (*sigs)[96],
+                                 const uint32_t *com, const uint32_t *pk_idx, const uint32_t *pk_off,
+                                 const uint64_t *rands, size_t n, int32_t *sig_status,
+                                 uint32_t call_flags) {
+  t_last_error = GBLS_ERR_NONE;
+  if (!sig_status) return fail(GBLS_ERR_ARG), GBLS_VERIFY_FAIL;
+  fill(sig_status, n, GBLS_BAD_ENCODING);
+  API_BEGIN
+  if (n == 0) return GBLS_VERIFY_FAIL;
+  if (!msgs || !sigs || !rands || !committee_args_ok(com, pk_idx, pk_off, n))
+    return fail(GBLS_ERR_ARG), GBLS_VERIFY_FAIL;
+  PkSource src;
+  src.com = com;
+  src.idx = pk_idx;
+  src.off = pk_off;
+  uint32_t off[2] = {0, (uint32_t)n};
+  int32_t v = GBLS_VERIFY_FAIL;
+  const int cls = (call_flags & GBLS_CALL_BLOCK) ? 1 : 0;
+  BlockActive block_active(cls != 0);
+  // its own submission (not queued with the coalescer's requests, which do not carry committees)
+  if (!verify_host(&msgs[0][0], nullptr, &sigs[0][0], sig_status, src, rands, n, off, 1, &v, cls)) {
+    fill(sig_status, n, GBLS_BAD_ENCODING);
+    return GBLS_VERIFY_FAIL;
+  }
+  for (size_t i = 0; i < n; i++)  // MultiVerifier::finish: a decoding error comes first
+    if (sig_status[i] != GBLS_SUCCESS) return sig_status[i];
+  return v;
 }
 
 int gbls_sk_to_pk(const uint8_t (*sks)[32], size_t n, gbls_p1_affine *out) {

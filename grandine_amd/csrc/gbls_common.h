@@ -85,6 +85,17 @@ void launch_g1_aggregate_idx(hipStream_t st, const g1a *reg, uint32_t nreg, cons
                              const uint32_t *off, uint32_t nseg, g1a *out, int32_t *status);
 void launch_g1_gather_idx(hipStream_t st, const g1a *reg, uint32_t nreg, const uint32_t *idx,
                           uint32_t n, g1a *out, int32_t *status);
+// k_committees.hip -- keys from cached committee sums: out[i] = tab[com[i]] - sum of
+// reg[idx[off[i] .. off[i+1])], or that sum itself when com[i] is kNoCommittee (gbls_committees.h).
+// max_len: the longest list (picks the launch form: lists of at least g_committee_row_min keys
+// run one 16-lane row per set, shorter ones one lane per set; GBLS_COMMITTEE_ROW_MIN).  12: the
+// measured crossover of an epoch-shaped launch (2048 sets: lanes 388 us vs rows 404 at 11 keys,
+// 405 vs 404 at 12, 439 vs 374 at 14; a 64-set launch crosses at 8)
+constexpr uint32_t kCommitteeRowMin = 12;
+extern uint32_t g_committee_row_min;
+void launch_g1_committee_keys(hipStream_t st, const g1a *reg, uint32_t nreg, const g1a *tab, uint32_t ntab,
+                              const uint32_t *com, const uint32_t *idx, const uint32_t *off, uint32_t n,
+                              uint32_t max_len, g1a *out, int32_t *status);
 void launch_sk_to_pk(hipStream_t st, const uint8_t *sks, uint32_t n, g1a *out);
 void launch_sign(hipStream_t st, const uint8_t *sks, const g2a *H, uint32_t n, g2a *out);
 void launch_mad_peak(hipStream_t st, unsigned blocks, uint64_t *sink, uint32_t iters, uint32_t seed);

@@ -116,6 +116,11 @@ struct KeySource {
   const G1 *pts = nullptr;        // points: one per set (off == nullptr) or summed per set
   const uint32_t *idx = nullptr;  // registry indices: one per set (off == nullptr) or summed
   const uint32_t *off = nullptr;  // per-set ranges [off[i], off[i+1]) of pts / idx
+  // cached committee sums (with idx and off): set i's key is committee slot com[i] MINUS its
+  // summed range, or the range's sum when com[i] names no committee.  Never merged by the
+  // coalescer (Request::kind does not know it): such a call is its own submission.
+  const uint32_t *com = nullptr;
+  uint32_t max_len = 0;           // ... and the longest range (a device source: the launch form)
 };
 
 // One caller's batch (host pointers, borrowed for the call).  rands == nullptr: independent

@@ -2,6 +2,7 @@
 // segment), key material for fixtures (a15) and the v_mad_u64_u32 roofline probe.
 #include "gbls_common.h"
 #include "bls_w4.h"
+#include "gbls_rowfold.h"
 
 namespace gbls {
 
@@ -135,20 +136,7 @@ __global__ void __launch_bounds__(WG) k_g1_gather_idx(const g1a *reg, uint32_t n
 // no barrier), and the row's lane 0 converts to affine: four segments per wave share
 // one inversion's latency, where the workgroup form spends a tree of 8 LDS levels and a
 // whole inversion per segment.
-template <int K>
-__device__ __forceinline__ uint32_t row_shl(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x100 + K, 0xf, 0xf, true);
-}
-template <int K, class F>
-__device__ __forceinline__ void jac_row_fold(jac<F> &acc, uint32_t &flag) {
-  jac<F> o;
-  uint32_t *d = reinterpret_cast<uint32_t *>(&o);
-  const uint32_t *a = reinterpret_cast<const uint32_t *>(&acc);
-#pragma unroll
-  for (int i = 0; i < (int)(sizeof(jac<F>) / 4); i++) d[i] = row_shl<K>(a[i]);
-  flag |= row_shl<K>(flag);
-  jac_add(acc, acc, o);  // lanes past the row end read zeros: infinity
-}
+// (row_shl / jac_row_fold: gbls_rowfold.h)
 // segment s = sum of pts[i] (idx == nullptr) or reg[idx[i]], i in [off[s], off[s+1])
 template <class F, bool X>
 __global__ void __launch_bounds__(WG) k_aggregate_rows(const aff<F> *pts, uint32_t nreg,

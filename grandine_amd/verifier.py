@@ -53,12 +53,18 @@ class VerifierOption(enum.Enum):
     BlockImport = 3  # the drop-in's one new option: the engine's block-import class (f3)
 
 
+# MultiVerifier.finish names a committee slot when the absentee list is shorter than this multiple
+# of the participant list (1: whichever list is shorter; tools/bench_committees.py measures where
+# the absentee form stops winning)
+ABSENTEE_FORM_MAX_RATIO = 1
+
+
 class Triple:
     """(message: H256, signature_bytes: SignatureBytes, public_key: PublicKey), or, after
     ``verify_aggregate``, the message, signature and the KEY LIST whose sum is the key."""
 
     IS_NULL = False
-    __slots__ = ("message", "signature_bytes", "_key", "deferred", "indices")
+    __slots__ = ("message", "signature_bytes", "_key", "deferred", "indices", "slot", "committee", "absent")
 
     def __init__(self, message: bytes = bytes(32), signature_bytes: bytes = None,
                  public_key: "bls.PublicKey" = None):
@@ -67,6 +73,9 @@ class Triple:
         self._key = public_key if public_key is not None else bls.PublicKey.default()
         self.deferred = None  # list of keys once verify_aggregate has run
         self.indices = None   # their validator indices (verify_aggregate_indexed, f1)
+        self.slot = None      # the committee table slot (verify_aggregate_committee), with
+        self.committee = None  # ... the committee's member indices
+        self.absent = None    # ... and the members whose aggregation bit is clear
 
     def verify_aggregate(self, message, signature_bytes, public_keys, signature_kind=None):
         """verifier.rs:387-405 without the reduce: the keys are kept and summed on the device by
@@ -76,6 +85,10 @@ class Triple:
         self.signature_bytes = bls.SignatureBytes(bytes(signature_bytes))
         self._key = bls.PublicKey.default()
         self.deferred = list(public_keys)
+        # a reused triple keeps nothing of its previous set (rust/bls_patch/verifier.rs resets
+        # its indices the same way)
+        self.indices = None
+        self.slot = self.committee = self.absent = None
 
     def verify_aggregate_indexed(self, message, signature_bytes, validator_indices, public_keys,
                                  signature_kind=None):
@@ -83,6 +96,24 @@ class Triple:
         (rust/bls_patch/verifier.rs), so MultiVerifier.finish can name registry slots."""
         self.verify_aggregate(message, signature_bytes, public_keys, signature_kind)
         self.indices = [int(i) for i in validator_indices]
+
+    def verify_aggregate_committee(self, message, signature_bytes, slot, committee, aggregation_bits,
+                                   public_keys, signature_kind=None):
+        """verify_aggregate_indexed for an attestation of a whole committee: ``committee`` (its
+        validator indices, helper_functions/src/accessors.rs:510-531) lives in committee table
+        slot ``slot`` (bls.Committees), ``aggregation_bits`` selects the participants and
+        ``public_keys`` are the participants' keys.  Keeps the participants' indices, as
+        verify_aggregate_indexed does, plus the slot, the committee and the absentees, so that
+        MultiVerifier.finish can send whichever list is shorter."""
+        committee = [int(i) for i in committee]
+        bits = [bool(b) for b in aggregation_bits]
+        if len(bits) != len(committee):
+            raise ValueError("one aggregation bit per committee member")
+        self.verify_aggregate_indexed(message, signature_bytes, [v for v, b in zip(committee, bits) if b],
+                                      public_keys, signature_kind)
+        self.slot = int(slot)
+        self.committee = committee
+        self.absent = [v for v, b in zip(committee, bits) if not b]
 
     @property
     def public_key(self) -> "bls.PublicKey":
@@ -182,7 +213,7 @@ class MultiVerifier(Verifier):
     def __init__(self, options: Iterable[VerifierOption] = (), triples: Optional[List[Triple]] = None):
         self.triples: List[Triple] = list(triples or [])
         self.options = set(options)
-        self.last_path = None  # "indices" or "points": the key form of the last finish (tests)
+        self.last_path = None  # "committees", "indices" or "points": the key form of the last finish (tests)
 
     @classmethod
     def from_triples(cls, triples: List[Triple]) -> "MultiVerifier":  # From<Vec<Triple>>
@@ -205,6 +236,13 @@ class MultiVerifier(Verifier):
         t.verify_aggregate_indexed(message, signature_bytes, validator_indices, public_keys, signature_kind)
         self.triples.append(t)
 
+    def verify_aggregate_committee(self, message, signature_bytes, slot, committee, aggregation_bits, public_keys,
+                                   signature_kind):
+        t = Triple()
+        t.verify_aggregate_committee(message, signature_bytes, slot, committee, aggregation_bits, public_keys,
+                                     signature_kind)
+        self.triples.append(t)
+
     def finish(self, randoms=None):
         """verifier.rs:301-323."""
         if not self.triples:
@@ -216,7 +254,20 @@ class MultiVerifier(Verifier):
         flags = 0x1 if VerifierOption.BlockImport in self.options else 0
         msgs = [t.message for t in self.triples]
         sigs = [t.signature_bytes for t in self.triples]
-        if all(t.indices is not None and bls.Registry.covers(t.indices) for t in self.triples):
+        indexed = all(t.indices is not None and bls.Registry.covers(t.indices) for t in self.triples)
+        com = [t for t in self.triples if t.slot is not None]
+        if indexed and com and all(bls.Committees.covers(t.slot, t.committee) and bls.Registry.covers(t.absent)
+                                   for t in com):
+            # cached committee sums: per committee triple the absentees (key = slot - their sum)
+            # or, when they are the longer list, the participants without a slot
+            self.last_path = "committees"
+            slots, lists = [], []
+            for t in self.triples:
+                by_absence = t.slot is not None and len(t.absent) < ABSENTEE_FORM_MAX_RATIO * len(t.indices)
+                slots.append(t.slot if by_absence else None)
+                lists.append(t.absent if by_absence else t.indices)
+            rc = bls.Signature.multi_verify_compressed_committees(msgs, sigs, slots, lists, randoms, flags)
+        elif indexed:
             self.last_path = "indices"
             rc = bls.Signature.multi_verify_compressed_indexed(msgs, sigs, [t.indices for t in self.triples],
                                                                randoms, flags)

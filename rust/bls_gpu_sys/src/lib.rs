@@ -20,7 +20,9 @@
 //!   the point.  No `transmute`, no reliance on the private layout of blst's wrapper types.
 #![deny(unsafe_op_in_unsafe_fn)]
 
+pub mod committees;
 pub mod ffi;
+pub mod ffi_committees;
 
 use core::{ffi::c_int, ptr};
 use std::sync::OnceLock;
