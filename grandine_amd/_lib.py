@@ -110,6 +110,14 @@ EXPORTS_COMMITTEES = [
     "gbls_g1_aggregate_committees",
     "gbls_multi_verify_committees",
 ]
+# include/grandine_bls_gpu_msgcache.h (message line cache)
+EXPORTS_MSGCACHE = [
+    "gbls_msgcache_configure",
+    "gbls_msgcache_slots",
+    "gbls_msgcache_clear",
+    "gbls_msgcache_stats",
+]
+MSGCACHE_STATS = ("lookups", "hits", "misses", "published", "evictions", "bypassed", "entries", "reserved")
 
 
 class EngineUnavailable(RuntimeError):
@@ -202,8 +210,16 @@ def load_library():
                 "gbls_g1_aggregate_committees": (_c.c_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
                 "gbls_multi_verify_committees": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp,
                                                             _c.c_uint32]),
+                "gbls_msgcache_configure": (_c.c_int, [_sz]),
+                "gbls_msgcache_slots": (_sz, []),
+                "gbls_msgcache_clear": (_c.c_int, []),
+                "gbls_msgcache_stats": (_c.c_int, [_vp]),
             }
             for name, (res, args) in sig.items():
+                # an experiment build (GBLS_LIB) may predate the message line cache: A/B tools load
+                # it and leave the four entries alone; the package's own library must have them
+                if _override and name in EXPORTS_MSGCACHE and not hasattr(lib, name):
+                    continue
                 fn = getattr(lib, name)
                 fn.restype = res
                 fn.argtypes = args

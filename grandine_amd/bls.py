@@ -525,3 +525,45 @@ class Committees:
     def forget(cls) -> None:
         """Tests: the process's engine table was cleared or overwritten by someone else."""
         cls._members = {}
+
+
+class MessageCache:
+    """The engine's message line cache (include/grandine_bls_gpu_msgcache.h): per device, a
+    device-resident table from a 32-byte message to its 68 Miller line events, so that a batch
+    verification whose messages were verified before skips hash_to_G2 and line generation for
+    them.  Off until ``configure(slots)``; 19 584 bytes per slot per device.  None of the calls
+    needs a device (the memory comes with the first served verification)."""
+
+    MAX_SLOTS = 1 << 20
+    BYTES_PER_SLOT = 68 * 72 * 4
+
+    @classmethod
+    def configure(cls, slots: int) -> None:
+        """gbls_msgcache_configure: the capacity in entries per device; 0 switches the cache off."""
+        slots = int(slots)
+        if not 0 <= slots <= cls.MAX_SLOTS:
+            raise ValueError("message cache slots must be in [0, 2^20]")
+        G.check(G.load_library().gbls_msgcache_configure(slots), "gbls_msgcache_configure")
+
+    @classmethod
+    def slots(cls) -> int:
+        return int(G.load_library().gbls_msgcache_slots())
+
+    @classmethod
+    def clear(cls) -> None:
+        """Drops every entry and keeps the capacity."""
+        G.check(G.load_library().gbls_msgcache_clear(), "gbls_msgcache_clear")
+
+    @classmethod
+    def stats(cls) -> dict:
+        """gbls_msgcache_stats as a dict: lookups, hits, misses, published, evictions, bypassed
+        (counters since the process started) and entries (now)."""
+        out = (ctypes.c_uint64 * 8)()
+        G.check(G.load_library().gbls_msgcache_stats(out), "gbls_msgcache_stats")
+        return {name: int(out[i]) for i, name in enumerate(G.MSGCACHE_STATS) if name != "reserved"}
+
+    @classmethod
+    def memory_bytes(cls, slots: int) -> int:
+        """Device memory per engine device at this capacity, spare slots included."""
+        slots = int(slots)
+        return 0 if slots == 0 else (slots + min(max(slots // 4, 64), 4096)) * cls.BYTES_PER_SLOT

@@ -35,9 +35,11 @@
 
 #include "../../include/grandine_bls_gpu.h"
 #include "../../include/grandine_bls_gpu_committees.h"
+#include "../../include/grandine_bls_gpu_msgcache.h"
 #include "gbls_common.h"
 #include "gbls_committees.h"
 #include "gbls_dedup.h"
+#include "gbls_msgcache.h"
 #include "gbls_sched.h"
 #include "gbls_tables.h"
 
@@ -126,12 +128,13 @@ struct Buf {
 // ---- optional per-stage timing (HIP events on the launch stream), for bench.py
 enum Stage {
   S_H2C_FIELD, S_H2C_MAP, S_H2C_CLEAR, S_G1MUL, S_G2MUL, S_G2SUM, S_LINES, S_LINES_S, S_ML_LEAF,
-  S_ML_REDUCE, S_ML_HORNER, S_FINAL, S_PK_GATHER, S_MSM, S_MSGSUM, S_COUNT
+  S_ML_REDUCE, S_ML_HORNER, S_FINAL, S_PK_GATHER, S_MSM, S_MSGSUM, S_LC_LOAD, S_LC_STORE, S_COUNT
 };
 const char *kStageNames[S_COUNT] = {"k_h2c_field", "k_h2c_map",   "k_h2c_clear", "k_mv_g1mul",
                                     "k_mv_g2mul",  "k_g2sum",      "k_lines",     "k_lines_S",
                                     "k_ml_group",  "k_ml_reduce",  "k_ml_horner", "k_final_verdict",
-                                    "k_pk_resolve", "k_msm",        "k_g1s_msgsum"};
+                                    "k_pk_resolve", "k_msm",        "k_g1s_msgsum", "k_linecache_load",
+                                    "k_linecache_store"};
 
 // GBLS_TRACE_STALLS=1: report host waits inside device entry points (diagnostics); every line
 // carries the call index (leases since gbls_init) and whether the lease created its context
@@ -257,6 +260,14 @@ struct Ctx {
   // the U unique messages in place of the n messages); consumed and reset by the pipeline
   const dedup::Plan *plan = nullptr;
   dedup::Plan plan_host;  // the plan object of this context's calls (its vectors keep their memory)
+  // per-call option of the next pipeline_partials on this lease: the shard runs on the message
+  // line cache (gbls_msgcache.h; c.plan is then mc_plan.groups).  mc_plan: the plan object of this
+  // context's calls; mc_tab: the device's table the call planned against, held from planning
+  // until mc_finish, after the call's host synchronisation
+  const msgcache::ShardPlan *mc = nullptr;
+  msgcache::ShardPlan mc_plan;
+  std::shared_ptr<struct McTable> mc_tab;
+  hipEvent_t ev_lines = nullptr, ev_store = nullptr;
   // Pinned staging for host tables and host inputs: a ring of kStageRing buffers, one per call,
   // each recycled only once the uploads of the call that used it have landed.  (One buffer made
   // every call wait on the host for the previous call's uploads, which are queued behind that
@@ -297,6 +308,8 @@ struct Ctx {
     for (Stage &r : ring) HIPCHK(hipEventCreateWithFlags(&r.ev, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&ev_reg, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&ev_grow, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&ev_lines, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&ev_store, hipEventDisableTiming));
     return true;
   }
   // CU-masked stream triple: mode 1 = main chain on the first `main_cus` CUs, sides on the
@@ -468,6 +481,33 @@ struct Ctx {
 // k_ml_group launches of more than this many waves per SIMD pick G to fill whole rounds
 constexpr uint32_t kMlRounds = 2;
 
+// ---- message line cache (include/grandine_bls_gpu_msgcache.h): one table per engine device, its
+// host index and its slot-major device memory (allocated at the device's first served call).
+// Calls hold their table by shared_ptr from planning until after their host synchronisation, so a
+// table replaced by gbls_msgcache_configure is freed only once no call that planned against it is
+// in flight -- behind its readers and writers, with no event bookkeeping.
+struct McTable {
+  msgcache::Index ix;
+  uint32_t *dev = nullptr;
+  int hipdev = -1;
+  uint64_t gen = 0;
+  ~McTable() {
+    if (!dev) return;
+    int cur = -1;
+    (void)hipGetDevice(&cur);
+    (void)hipSetDevice(hipdev);
+    (void)hipFree(dev);
+    if (cur >= 0) (void)hipSetDevice(cur);
+  }
+};
+struct MsgCache {
+  std::mutex mu;               // the configuration, every device's index and the counters
+  std::atomic<bool> on{false};  // slots != 0 (read without the lock on every host batch)
+  size_t slots = 0;
+  uint64_t gen = 1;             // gbls_msgcache_configure starts a new one: fresh tables
+  uint64_t st[msgcache::kStats] = {0};
+} mcache;
+
 struct Device {
   int hipdev = -1;
   uint32_t nsimd = 1024;  // 4 SIMDs per CU
@@ -494,6 +534,7 @@ struct Device {
   // reg_ev, the readers' Ctx::ev_reg); each device sums its slots from its own registry replica.
   Buf com;
   bool com_pooled = false;
+  std::shared_ptr<McTable> mc_tab;  // message line cache table (guarded by mcache.mu)
 };
 
 struct Engine {
@@ -879,7 +920,14 @@ bool pipeline_partials(Ctx &c, Device &d, const uint8_t *msgs, const uint32_t *m
   const dedup::Plan *pl = c.plan;
   c.plan = nullptr;
   if (pl && (!rands || pl->n != n || pl->nseg != nseg)) return fail(GBLS_ERR_ARG);
-  const size_t nq = pl ? pl->ngroups : n;  // set-side Miller pairs = messages hashed
+  // message line cache: the groups that missed are pairs [0, nm), hashed and given lines as ever;
+  // the groups that hit are pairs [nm, nq), their lines copied from the cache table
+  const msgcache::ShardPlan *mcp = c.mc;
+  c.mc = nullptr;
+  if (mcp && (!pl || pl != &mcp->groups || !c.mc_tab || !c.mc_tab->dev)) return fail(GBLS_ERR_ARG);
+  const uint32_t *pair_of = mcp ? mcp->pair_of.data() : nullptr;  // group -> pair
+  const size_t nq = pl ? pl->ngroups : n;  // set-side Miller pairs (= messages hashed without the cache)
+  const size_t nm = mcp ? mcp->M : nq;     // messages hashed, pairs whose lines are generated
   bool single = !rands && n == nseg;  // one set per segment, r = 1
   for (size_t s = 0; single && s <= nseg; s++) single = seg_off[s] == s;
   // bucket MSM for S when every segment is large (segment sizes >= msm_min)
@@ -929,7 +977,8 @@ bool pipeline_partials(Ctx &c, Device &d, const uint8_t *msgs, const uint32_t *m
         tab, nseg, np, EC, d.nsimd, g.ml_rounds, g.ml_g,
         [&](size_t s) { return pl->grp_seg_off[s + 1] - pl->grp_seg_off[s] + (uint32_t)X; },
         [&](size_t s, std::vector<uint32_t> &t) {
-          for (uint32_t i = pl->grp_seg_off[s]; i < pl->grp_seg_off[s + 1]; i++) t.push_back(i);
+          for (uint32_t i = pl->grp_seg_off[s]; i < pl->grp_seg_off[s + 1]; i++)
+            t.push_back(pair_of ? pair_of[i] : i);
           for (size_t k = 0; k < X; k++) t.push_back((uint32_t)(nq + s * X + k));
         });
   else
@@ -964,6 +1013,17 @@ bool pipeline_partials(Ctx &c, Device &d, const uint8_t *msgs, const uint32_t *m
   tab.insert(tab.end(), seg_chunk.begin(), seg_chunk.end());
   const size_t segoff_at = tab.size();
   tab.insert(tab.end(), seg_off, seg_off + nseg + 1);
+  // message line cache: the groups' CSR in pair order and [hit slots][store pairs][store slots] ride
+  // in the same upload (no copy of their own on the main stream, ahead of the first kernel)
+  size_t mc_csr_at = 0, mc_ix_at = 0;
+  if (mcp) {
+    mc_csr_at = tab.size();
+    tab.insert(tab.end(), mcp->csr.begin(), mcp->csr.end());
+    mc_ix_at = tab.size();
+    tab.insert(tab.end(), mcp->hit_slot.begin(), mcp->hit_slot.end());
+    tab.insert(tab.end(), mcp->store_pair.begin(), mcp->store_pair.end());
+    tab.insert(tab.end(), mcp->store_slot.begin(), mcp->store_slot.end());
+  }
   // ---- workspaces
   if (sliced && !c.ensure(c.Ts, np * sizeof(g2h))) return false;
   if (sig_groupcheck && !c.ensure(c.pre2, n * sizeof(int32_t) + 16)) return false;
@@ -980,9 +1040,12 @@ bool pipeline_partials(Ctx &c, Device &d, const uint8_t *msgs, const uint32_t *m
       !c.ensure(c.hparts, 4 * 64 * sizeof(fp12)))  // the split Horner's parts (<= 64 segments)
     return false;
   if (!c.upload_staged(c.tab, tab.data(), tab.size() * 4, st)) return false;
-  const uint32_t N = (uint32_t)n, NP = (uint32_t)np, NS = (uint32_t)nseg, NQ = (uint32_t)nq;
+  const uint32_t N = (uint32_t)n, NP = (uint32_t)np, NS = (uint32_t)nseg, NQ = (uint32_t)nq, NM = (uint32_t)nm;
+  const uint32_t n_store = mcp ? (uint32_t)mcp->store_pair.size() : 0;
+  const bool hash_msgs = !mcp || NM;  // a call whose messages all hit has no hash_to_G2 and no set-side lines
   if (pl && trace_dedup())
-    fprintf(stderr, "gbls dedup: sets=%zu segments=%zu groups=%zu pairs=%zu\n", n, nseg, nq, np);
+    fprintf(stderr, "gbls dedup: sets=%zu segments=%zu groups=%zu pairs=%zu%s\n", n, nseg, nq, np,
+            mcp ? " (line cache)" : "");
   // latency regime: each segment's S = sum r_i sig_i stays Jacobian (no inversion), its lines
   // taken projectively (k_lines_w4j)
   g2j *sj = nullptr;
@@ -1001,13 +1064,17 @@ bool pipeline_partials(Ctx &c, Device &d, const uint8_t *msgs, const uint32_t *m
   HIPCHK(hipStreamWaitEvent(side1, c.ev_fork, 0));
   HIPCHK(hipStreamWaitEvent(side2, c.ev_fork, 0));
   // main stream first: its first kernels reach the GPU before the side streams' floods
-  {
-    StageTimer t(S_H2C_FIELD, st);
-    launch_h2c_field(st, msgs, msg_off, NQ, nullptr, 0, c.U.as<fp2>());
+  if (mcp && NQ > NM) {  // the hits' lines, from the cache table into their columns
+    StageTimer t(S_LC_LOAD, st);
+    launch_linecache_load(st, c.mc_tab->dev, T + mc_ix_at, NM, NQ - NM, lc, c.lines.as<uint32_t>());
   }
-  {
+  if (hash_msgs) {
+    StageTimer t(S_H2C_FIELD, st);
+    launch_h2c_field(st, msgs, msg_off, NM, nullptr, 0, c.U.as<fp2>());
+  }
+  if (hash_msgs) {
     StageTimer t(S_H2C_MAP, st);
-    launch_h2c_map(st, c.U.as<fp2>(), 2 * NQ, c.Q.as<g2j>());
+    launch_h2c_map(st, c.U.as<fp2>(), 2 * NM, c.Q.as<g2j>());
   }
   const g1a *pks = nullptr;
   const int32_t *pre = nullptr;
@@ -1019,7 +1086,7 @@ bool pipeline_partials(Ctx &c, Device &d, const uint8_t *msgs, const uint32_t *m
   }
   if (pl) {  // each group's point: the sum of its members' r_i pk_i
     StageTimer t(S_MSGSUM, side1);
-    const uint32_t *csr = c.in6.as<uint32_t>();
+    const uint32_t *csr = mcp ? T + mc_csr_at : c.in6.as<uint32_t>();
     launch_g1s_msgsum(side1, c.Pset.as<g1s>(), csr, csr + NQ + 1, NQ, pl->max_group, c.P.as<g1s>());
   }
   const int32_t *pre2 = nullptr;
@@ -1072,19 +1139,33 @@ bool pipeline_partials(Ctx &c, Device &d, const uint8_t *msgs, const uint32_t *m
   }
   // latency regime: H(m) stays Jacobian (over Q[2 i]) and its lines take it projectively,
   // no inversion on the main chain
-  const bool jac_h = !sliced && NQ <= kW4Max;
-  {
+  const bool jac_h = !sliced && NM <= kW4Max;
+  if (hash_msgs) {
     StageTimer t(S_H2C_CLEAR, st);
-    if (!jac_h || !launch_h2c_clear_jac(st, c.Q.as<g2j>(), NQ))
-      launch_h2c_clear(st, c.Q.as<g2j>(), NQ, c.H.as<g2a>());
+    if (!jac_h || !launch_h2c_clear_jac(st, c.Q.as<g2j>(), NM))
+      launch_h2c_clear(st, c.Q.as<g2j>(), NM, c.H.as<g2a>());
   }
-  {  // the sets' lines of the first event slice, before the join
+  if (hash_msgs) {  // the sets' lines of the first event slice, before the join
     StageTimer t(S_LINES, st);
-    if (!jac_h || !launch_lines_jac(st, c.Q.as<g2j>(), 2, 0, NQ, lc, c.lines.as<uint32_t>()))
-      launch_lines(st, c.H.as<g2a>(), 0, NQ, lc, 0, EC, c.Ts.as<g2h>(), c.lines.as<uint32_t>());
+    if (!jac_h || !launch_lines_jac(st, c.Q.as<g2j>(), 2, 0, NM, lc, c.lines.as<uint32_t>()))
+      launch_lines(st, c.H.as<g2a>(), 0, NM, lc, 0, EC, c.Ts.as<g2h>(), c.lines.as<uint32_t>());
   }
   HIPCHK(hipEventRecord(c.ev_side1, side1));
   HIPCHK(hipEventRecord(c.ev_side2, side2));
+  if (n_store) {
+    // The misses' lines go to their cache slots on side stream 1, which is idle from here on:
+    // behind the lines (ev_lines), beside the Miller product, off the path to the verdict.  The
+    // main stream waits for the copy only at its very end, so that the call's completion (the
+    // caller's host wait, and ev_done for the context's next use) covers it.
+    HIPCHK(hipEventRecord(c.ev_lines, st));
+    HIPCHK(hipStreamWaitEvent(side1, c.ev_lines, 0));
+    {
+      StageTimer t(S_LC_STORE, side1);
+      const uint32_t *ix = T + mc_ix_at + (NQ - NM);
+      launch_linecache_store(side1, c.mc_tab->dev, ix, ix + n_store, n_store, lc, c.lines.as<uint32_t>());
+    }
+    HIPCHK(hipEventRecord(c.ev_store, side1));
+  }
   HIPCHK(hipStreamWaitEvent(st, c.ev_side1, 0));
   HIPCHK(hipStreamWaitEvent(st, c.ev_side2, 0));
   if (lines_s_main) {
@@ -1115,6 +1196,7 @@ bool pipeline_partials(Ctx &c, Device &d, const uint8_t *msgs, const uint32_t *m
                     T + mt.grp_off, (uint32_t)mt.ngroup, e0, e1, c.V0.as<fp12>(), c.V28.as<uint32_t>(), pcn);
   }
   ml_tail(c, st, mt, T, (uint32_t)nms, partials, n <= kSplitHornerMaxSets);
+  if (n_store) HIPCHK(hipStreamWaitEvent(st, c.ev_store, 0));
   if (st != caller) {
     HIPCHK(hipEventRecord(c.ev_out, st));
     HIPCHK(hipStreamWaitEvent(caller, c.ev_out, 0));
@@ -1290,6 +1372,57 @@ bool upload_pks(Ctx &c, const PkSource &host, size_t b, size_t e, hipStream_t st
   return true;
 }
 
+// ----- message line cache, host side (the index and its rules: gbls_msgcache.h)
+// After c.mc_plan's groups are known: look the shard's distinct messages up in d's table (created,
+// with its device memory, at the first call after a configure) and number the pairs.  *cached:
+// the pipeline runs on the plan.  A sliced submission, or a cache switched off meanwhile, is not
+// served (the former counts its sets as bypassed).
+bool mc_plan_shard(Ctx &c, Device &d, bool unsliced, size_t n, bool *cached) {
+  *cached = false;
+  std::shared_ptr<McTable> old;  // a replaced table is released outside the lock
+  std::lock_guard<std::mutex> lk(mcache.mu);
+  if (!mcache.slots) return true;
+  if (!unsliced) {
+    mcache.st[msgcache::BYPASSED] += n;
+    return true;
+  }
+  if (!d.mc_tab || d.mc_tab->gen != mcache.gen) {
+    old = std::move(d.mc_tab);
+    std::shared_ptr<McTable> t = std::make_shared<McTable>();
+    const uint32_t spare = msgcache::spare_for(mcache.slots);
+    t->hipdev = d.hipdev;
+    t->gen = mcache.gen;
+    if (hipMalloc(reinterpret_cast<void **>(&t->dev), (mcache.slots + spare) * msgcache::kSlotWords * 4) !=
+        hipSuccess) {
+      t->dev = nullptr;
+      (void)hipGetLastError();
+      return fail(GBLS_ERR_HIP);
+    }
+    t->ix.reset((uint32_t)mcache.slots, spare, mcache.st);
+    d.mc_tab = std::move(t);
+  }
+  c.mc_tab = d.mc_tab;
+  msgcache::plan_cache(c.mc_plan, &c.mc_tab->ix);
+  *cached = true;
+  return true;
+}
+// After the call's host synchronisation (or its failure): unpin the hits, publish the misses whose
+// verdict was GBLS_SUCCESS -- per segment from seg_verdicts (host), or all of them when all_ok
+// (seg_verdicts == nullptr: the one-batch multi-device branch, and failures with all_ok false).
+void mc_finish(Ctx &c, const int32_t *seg_verdicts, bool all_ok) {
+  msgcache::ShardPlan &sp = c.mc_plan;
+  std::shared_ptr<McTable> tab = std::move(c.mc_tab);  // released outside the lock
+  if (!sp.txn.active || !tab) return;
+  std::vector<uint8_t> &seg_ok = sp.seg_ok;
+  if (seg_verdicts) {
+    seg_ok.resize(sp.groups.nseg);
+    for (uint32_t s = 0; s < sp.groups.nseg; s++) seg_ok[s] = seg_verdicts[s] == GBLS_SUCCESS;
+  }
+  msgcache::plan_verdicts(sp, seg_verdicts ? seg_ok.data() : nullptr, all_ok);
+  std::lock_guard<std::mutex> lk(mcache.mu);
+  tab->ix.finish(sp.txn, sp.ok.data());
+}
+
 // One device: host batch [sets b..e) in segments seg (rebased, host) -> per-segment
 // verdicts (host) when `verdicts`, or else the Miller partial + error flag of the single
 // segment, copied device-to-device (hipMemcpyPeerAsync, xGMI) to part_dst / err_dst on
@@ -1308,11 +1441,22 @@ bool enqueue_host_batch(Ctx &c, Device &d, const uint8_t *msgs, const g2a *sigs,
   // when the line buffer would be sliced (C5 scale), the plain path below runs unchanged.
   dedup::Plan &plan = c.plan_host;
   bool grouped_msgs = false;
-  if (!single && n > 1 && g.dedup.load(std::memory_order_relaxed)) {
+  // Message line cache: the shard is planned by message whatever the policy bit says (the cache
+  // needs the plan's indirection between sets and pairs); a sliced submission bypasses it.
+  msgcache::ShardPlan &sp = c.mc_plan;
+  bool cached = false;
+  if (sp.txn.active) mc_finish(c, nullptr, false);  // (never: every call ends in mc_finish)
+  if (!single && n > 0 && mcache.on.load(std::memory_order_relaxed)) {
+    msgcache::plan_groups(sp, msgs + 32 * b, n, seg, nseg);
+    if (!mc_plan_shard(c, d, lines_unsliced(sp.U, n, seg, nseg), n, &cached)) return false;
+  }
+  if (!cached && !single && n > 1 && g.dedup.load(std::memory_order_relaxed)) {
     dedup::build(plan, msgs + 32 * b, n, seg, nseg);
     grouped_msgs = plan.has_duplicates() && lines_unsliced(plan.ngroups, n, seg, nseg);
   }
-  if (grouped_msgs) {  // the unique messages in place of the n messages, and the groups' CSR
+  if (cached) {  // the messages that missed (the plan's tables go up with the pipeline's)
+    if (!c.upload_staged(c.in0, sp.miss_msgs.data(), sp.miss_msgs.size(), st)) return false;
+  } else if (grouped_msgs) {  // the unique messages in place of the n messages, and the groups' CSR
     std::vector<uint32_t> &csr = c.host_tab;
     csr.assign(plan.grp_off.begin(), plan.grp_off.end());
     csr.insert(csr.end(), plan.grp_set.begin(), plan.grp_set.end());
@@ -1343,7 +1487,8 @@ bool enqueue_host_batch(Ctx &c, Device &d, const uint8_t *msgs, const g2a *sigs,
   }
   bool ok;
   const uint64_t *drands = single ? nullptr : c.in3.as<uint64_t>();
-  c.plan = grouped_msgs ? &plan : nullptr;
+  c.plan = cached ? &sp.groups : grouped_msgs ? &plan : nullptr;
+  c.mc = cached ? &sp : nullptr;
   if (verdicts)
     ok = c.ensure(c.out1, nseg * sizeof(int32_t)) &&
          pipeline_verdicts(c, d, c.in0.as<uint8_t>(), nullptr, dsigs, dsrc, drands, single, n, seg,
@@ -1355,6 +1500,7 @@ bool enqueue_host_batch(Ctx &c, Device &d, const uint8_t *msgs, const g2a *sigs,
   c.sig_c = nullptr;  // the options are for this call only, consumed or not
   c.sig_st = nullptr;
   c.plan = nullptr;
+  c.mc = nullptr;
   if (!ok) return false;
   if (verdicts) {
     HIPCHK(hipMemcpyAsync(verdicts, c.out1.p, nseg * 4, hipMemcpyDeviceToHost, st));
@@ -1423,6 +1569,8 @@ bool verify_host(const uint8_t *msgs, const g2a *sigs, const uint8_t *sigs_c, in
     if (ok && hipStreamSynchronize(st0) != hipSuccess) ok = fail(GBLS_ERR_HIP);
     if (!ok)
       for (auto &L : leases) (void)hipStreamSynchronize((*L)->own);
+    // message line cache: every shard's misses are published on the batch's verdict
+    for (auto &L : leases) mc_finish(**L, nullptr, ok && verdicts[0] == GBLS_SUCCESS);
     for (hipEvent_t ev : evs) (void)hipEventDestroy(ev);
     return ok;
   }
@@ -1454,6 +1602,11 @@ bool verify_host(const uint8_t *msgs, const g2a *sigs, const uint8_t *sigs_c, in
   rl.unlock();  // enqueued: the host waits do not hold up registry updates
   for (auto &L : leases)
     if (hipStreamSynchronize((*L)->own) != hipSuccess) ok = fail(GBLS_ERR_HIP);
+  // message line cache: each shard publishes the misses of its segments that passed
+  for (size_t j = 0, l = 0; j < k && l < leases.size(); j++) {
+    if (cut[j + 1] == cut[j]) continue;
+    mc_finish(**leases[l++], ok ? verdicts + cut[j] : nullptr, false);
+  }
   return ok;
 }
 
@@ -2468,6 +2621,49 @@ int gbls_multi_verify_committees(const uint8_t (*msgs)[32], const uint8_t (*sigs
   for (size_t i = 0; i < n; i++)  // MultiVerifier::finish: a decoding error comes first
     if (sig_status[i] != GBLS_SUCCESS) return sig_status[i];
   return v;
+}
+
+// ---- message line cache (include/grandine_bls_gpu_msgcache.h).  None of these needs a device:
+// a table and its device memory come with the first served call on each engine device.
+int gbls_msgcache_configure(size_t slots) {
+  t_last_error = GBLS_ERR_NONE;
+  if (slots > msgcache::kMaxSlots) return fail(GBLS_ERR_ARG), FAILED;
+  std::vector<std::shared_ptr<McTable>> old;  // released outside the lock, each once its calls are done
+  std::lock_guard<std::mutex> lk(mcache.mu);
+  if (slots == mcache.slots) return GBLS_SUCCESS;
+  mcache.slots = slots;
+  mcache.gen++;
+  mcache.on.store(slots != 0);
+  if (g.ready.load())
+    for (auto &d : g.devs) old.push_back(std::move(d->mc_tab));
+  return GBLS_SUCCESS;
+}
+
+size_t gbls_msgcache_slots(void) {
+  std::lock_guard<std::mutex> lk(mcache.mu);
+  return mcache.slots;
+}
+
+int gbls_msgcache_clear(void) {
+  t_last_error = GBLS_ERR_NONE;
+  std::lock_guard<std::mutex> lk(mcache.mu);
+  if (g.ready.load())
+    for (auto &d : g.devs)
+      if (d->mc_tab) d->mc_tab->ix.clear();
+  return GBLS_SUCCESS;
+}
+
+int gbls_msgcache_stats(uint64_t out[8]) {
+  t_last_error = GBLS_ERR_NONE;
+  if (!out) return fail(GBLS_ERR_ARG), FAILED;
+  std::lock_guard<std::mutex> lk(mcache.mu);
+  for (int i = 0; i < msgcache::kStats; i++) out[i] = mcache.st[i];
+  out[6] = 0;
+  if (g.ready.load())
+    for (auto &d : g.devs)
+      if (d->mc_tab && d->mc_tab->gen == mcache.gen) out[6] += d->mc_tab->ix.entries;
+  out[7] = 0;
+  return GBLS_SUCCESS;
 }
 
 int gbls_sk_to_pk(const uint8_t (*sks)[32], size_t n, gbls_p1_affine *out) {

@@ -185,6 +185,14 @@ void launch_lines(hipStream_t st, const g2a *H, uint32_t first, uint32_t count, 
 bool launch_lines_jac(hipStream_t st, const g2j *Qj, uint32_t stride, uint32_t first, uint32_t count,
                       LineCols lc, uint32_t *lines);
 
+// k_linecache.hip -- message line cache (gbls_msgcache.h): tab is slot-major, 68 x 72 words per slot
+// the lines of pairs [first, first + count) from slots slot[0 .. count) into their columns
+void launch_linecache_load(hipStream_t st, const uint32_t *tab, const uint32_t *slot, uint32_t first,
+                           uint32_t count, LineCols lc, uint32_t *lines);
+// the lines of pairs pairs[0 .. count) from their columns into slots slot[0 .. count)
+void launch_linecache_store(hipStream_t st, uint32_t *tab, const uint32_t *pairs, const uint32_t *slot,
+                            uint32_t count, LineCols lc, const uint32_t *lines);
+
 // k_miller.hip -- Miller product tree + Horner
 // groups: (first index into plist, stride, count) per group, segment by segment
 // events [e0, e1): lines at event e - e0, products to V0[e * ngroup + g]; the lines of pair j

@@ -23,6 +23,8 @@
 pub mod committees;
 pub mod ffi;
 pub mod ffi_committees;
+pub mod ffi_msgcache;
+pub mod msgcache;
 
 use core::{ffi::c_int, ptr};
 use std::sync::OnceLock;
