@@ -110,6 +110,13 @@ EXPORTS_COMMITTEES = [
     "gbls_g1_aggregate_committees",
     "gbls_multi_verify_committees",
 ]
+# include/grandine_bls_gpu_bits.h (aggregation-bit sets over resident committee members)
+EXPORTS_BITS = [
+    "gbls_committees_set_members",
+    "gbls_committees_members",
+    "gbls_g1_aggregate_bits",
+    "gbls_multi_verify_bits",
+]
 # include/grandine_bls_gpu_msgcache.h (message line cache)
 EXPORTS_MSGCACHE = [
     "gbls_msgcache_configure",
@@ -210,15 +217,21 @@ def load_library():
                 "gbls_g1_aggregate_committees": (_c.c_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
                 "gbls_multi_verify_committees": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp,
                                                             _c.c_uint32]),
+                "gbls_committees_set_members": (_c.c_int, [_sz, _vp, _vp, _sz, _vp]),
+                "gbls_committees_members": (_sz, [_sz]),
+                "gbls_g1_aggregate_bits": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+                "gbls_multi_verify_bits": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp,
+                                                      _c.c_uint32]),
                 "gbls_msgcache_configure": (_c.c_int, [_sz]),
                 "gbls_msgcache_slots": (_sz, []),
                 "gbls_msgcache_clear": (_c.c_int, []),
                 "gbls_msgcache_stats": (_c.c_int, [_vp]),
             }
             for name, (res, args) in sig.items():
-                # an experiment build (GBLS_LIB) may predate the message line cache: A/B tools load
-                # it and leave the four entries alone; the package's own library must have them
-                if _override and name in EXPORTS_MSGCACHE and not hasattr(lib, name):
+                # an experiment build (GBLS_LIB) may predate the message line cache or the bits
+                # calls: A/B tools load it and leave those entries alone; the package's own library
+                # must have them
+                if _override and name in EXPORTS_MSGCACHE + EXPORTS_BITS and not hasattr(lib, name):
                     continue
                 fn = getattr(lib, name)
                 fn.restype = res

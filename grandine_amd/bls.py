@@ -346,6 +346,40 @@ class Signature:
             G.u32_array(off), G.u64_array(randoms), n, st, call_flags)
 
     @staticmethod
+    def multi_verify_compressed_bits(messages: Iterable[bytes], signature_bytes: Iterable[bytes],
+                                     committee_slots: Iterable[int], bitfields: Iterable[bytes],
+                                     validator_indices: Iterable[Sequence[int]],
+                                     randoms: Sequence[int] = None, call_flags: int = 0) -> int:
+        """multi_verify_compressed_committees with the sets given as they arrive
+        (gbls_multi_verify_bits): set i names committee slot ``committee_slots[i]``, loaded with its
+        members (Committees.set(..., members=True)), and carries its SSZ aggregation bits
+        ``bitfields[i]`` (a Bitlist with its delimiter, or a Bitvector); its key is the sum of the
+        members whose bit is set.  A set whose slot is ``None`` is the plain sum of the registry
+        keys ``validator_indices[i]`` and has no bits.  Returns as multi_verify_compressed."""
+        msgs = [bytes(m) for m in messages]
+        sigs = [bytes(s) for s in signature_bytes]
+        com = [G.NO_COMMITTEE if c is None else int(c) for c in committee_slots]
+        fields = [bytes(b or b"") for b in bitfields]
+        idx = [list(v or ()) for v in validator_indices]
+        n = len(sigs)
+        if n == 0 or len(msgs) != n or len(idx) != n or len(com) != n or len(fields) != n:
+            return G.VERIFY_FAIL
+        if any(len(m) != 32 for m in msgs) or any(len(s) != 96 for s in sigs):
+            raise ValueError("messages must be 32-byte signing roots and signatures 96 bytes")
+        if randoms is None:
+            randoms = [secrets.randbits(64) or 1 for _ in range(n)]
+        off, boff = [0], [0]
+        for v, b in zip(idx, fields):
+            off.append(off[-1] + len(v))
+            boff.append(boff[-1] + len(b))
+        flat = [i for v in idx for i in v]
+        L = G.lib()
+        st = G.i32_array(n)
+        return L.gbls_multi_verify_bits(
+            G.buf(b"".join(msgs)), G.buf(b"".join(sigs)), G.u32_array(com), G.buf(b"".join(fields)),
+            G.u32_array(boff), G.u32_array(flat or [0]), G.u32_array(off), G.u64_array(randoms), n, st, call_flags)
+
+    @staticmethod
     def verify_batch_compressed(messages: Iterable[bytes], signature_bytes: Iterable[bytes],
                                 public_keys: Iterable) -> List:
         """SingleVerifier::extend's try_from + verify per triple (verifier.rs:215-236) as ONE
@@ -484,14 +518,19 @@ class Committees:
     """The engine's cached committee key sums (include/grandine_bls_gpu_committees.h): slot s holds
     the sum of one committee's registry keys, loaded once per epoch (the sync committee once per
     period), so that a set's key is the slot minus its few ABSENT members.  The mirror remembers
-    each loaded slot's member list; ``covers`` says whether a triple may name the slot."""
+    each loaded slot's member list; ``covers`` says whether a triple may name the slot.  With
+    ``members=True`` the engine keeps the member lists as well (include/grandine_bls_gpu_bits.h), so
+    that a set is the slot and its aggregation bits; ``has_members`` says which slots those are."""
 
     _members = {}  # slot -> tuple of validator indices, for slots loaded with status SUCCESS
+    _resident = set()  # the slots among them whose member lists the engine keeps
 
     @classmethod
-    def set(cls, first: int, committees: Sequence[Sequence[int]]) -> List[int]:
+    def set(cls, first: int, committees: Sequence[Sequence[int]], members: bool = False) -> List[int]:
         """gbls_committees_set: committees[c] (validator indices) into slot first + c.  Returns
-        the per-committee statuses; only SUCCESS slots are remembered (the others are invalid)."""
+        the per-committee statuses; only SUCCESS slots are remembered (the others are invalid).
+        members=True: gbls_committees_set_members, the slots keep their member lists on the device;
+        else the slots' resident members, if any, are dropped."""
         coms = [[int(i) for i in c] for c in committees]
         off = [0]
         for c in coms:
@@ -500,12 +539,21 @@ class Committees:
         st = G.i32_array(len(coms))
         for c in range(len(coms)):
             cls._members.pop(first + c, None)
-        G.check(L.gbls_committees_set(first, G.u32_array([i for c in coms for i in c] or [0]), G.u32_array(off),
-                                      len(coms), st), "gbls_committees_set")
-        for c, members in enumerate(coms):
+            cls._resident.discard(first + c)
+        call = L.gbls_committees_set_members if members else L.gbls_committees_set
+        G.check(call(first, G.u32_array([i for c in coms for i in c] or [0]), G.u32_array(off),
+                     len(coms), st), "gbls_committees_set_members" if members else "gbls_committees_set")
+        for c, com in enumerate(coms):
             if st[c] == G.SUCCESS:
-                cls._members[first + c] = tuple(members)
+                cls._members[first + c] = tuple(com)
+                if members:
+                    cls._resident.add(first + c)
         return [st[c] for c in range(len(coms))]
+
+    @classmethod
+    def has_members(cls, slot: int) -> bool:
+        """True when ``slot`` was loaded with members=True (and not rewritten without since)."""
+        return slot is not None and int(slot) in cls._resident
 
     @classmethod
     def size(cls) -> int:
@@ -514,6 +562,7 @@ class Committees:
     @classmethod
     def clear(cls) -> None:
         cls._members = {}
+        cls._resident = set()
         G.check(G.lib().gbls_committees_clear(), "gbls_committees_clear")
 
     @classmethod
@@ -525,6 +574,7 @@ class Committees:
     def forget(cls) -> None:
         """Tests: the process's engine table was cleared or overwritten by someone else."""
         cls._members = {}
+        cls._resident = set()
 
 
 class MessageCache:

@@ -36,9 +36,12 @@
 #include "../../include/grandine_bls_gpu.h"
 #include "../../include/grandine_bls_gpu_committees.h"
 #include "../../include/grandine_bls_gpu_msgcache.h"
+#include "../../include/grandine_bls_gpu_bits.h"
 #include "gbls_common.h"
+#include "gbls_bits.h"
 #include "gbls_committees.h"
 #include "gbls_dedup.h"
+#include "gbls_members.h"
 #include "gbls_msgcache.h"
 #include "gbls_sched.h"
 #include "gbls_tables.h"
@@ -467,11 +470,20 @@ struct Ctx {
   }
   bool upload_staged(Buf &dst, const void *host, size_t bytes, hipStream_t st) {
     if (!ensure(dst, bytes + 16)) return false;
+    return upload_to(dst.p, host, bytes, st);
+  }
+  // ... into device memory the caller owns
+  bool upload_to(void *dst, const void *host, size_t bytes, hipStream_t st) {
     if (!bytes) return true;
     void *s = staging(bytes);
     if (!s) return fail(GBLS_ERR_HIP);
     std::memcpy(s, host, bytes);
-    HIPCHK(hipMemcpyAsync(dst.p, s, bytes, hipMemcpyHostToDevice, st));
+    return send_staged(dst, s, bytes, st);
+  }
+  // ... from a region of this call's staging buffer that the caller has filled
+  bool send_staged(void *dst, const void *s, size_t bytes, hipStream_t st) {
+    if (!bytes) return true;
+    HIPCHK(hipMemcpyAsync(dst, s, bytes, hipMemcpyHostToDevice, st));
     HIPCHK(hipEventRecord(ring[stage_at].ev, st));
     ring[stage_at].pending = true;
     return true;
@@ -534,6 +546,13 @@ struct Device {
   // reg_ev, the readers' Ctx::ev_reg); each device sums its slots from its own registry replica.
   Buf com;
   bool com_pooled = false;
+  // resident member lists (replica): the device memory of each block of Engine::mem, by block id
+  // (gbls_members.h); written on reg_st by gbls_committees_set_members, freed by block_retire
+  struct MemBlock {
+    void *p = nullptr;
+    bool pooled = false;
+  };
+  std::vector<MemBlock> mem_blocks;
   std::shared_ptr<McTable> mc_tab;  // message line cache table (guarded by mcache.mu)
 };
 
@@ -545,6 +564,7 @@ struct Engine {
   std::shared_mutex reg_mu;
   size_t reg_n = 0;
   size_t com_n = 0;  // committee table slots (guarded by reg_mu)
+  members::Table mem;  // which slots keep their member lists, and in which block (guarded by reg_mu)
   std::atomic<bool> coalesce{true};
   std::atomic<bool> per_check{false};  // GBLS_INIT_PER_CHECK: no grouped single checks
   std::atomic<bool> dedup{false};      // GBLS_INIT_DEDUP: host batches grouped by message
@@ -823,7 +843,10 @@ bool resolve_pks(Ctx &c, Device &d, const PkSource &src, size_t n, hipStream_t s
   StageTimer t(S_PK_GATHER, st);
   const g1a *reg = d.reg.as<g1a>();
   if (src.idx && !registry_read_begin(c, d, st)) return false;
-  if (src.com)  // cached committee sums minus the listed keys (the table is read as the registry is)
+  if (src.bit_sets)  // resident members chosen by aggregation bits (member blocks: read as the registry is)
+    launch_g1_bits_keys(st, reg, (uint32_t)g.reg_n, d.com.as<g1a>(), (uint32_t)g.com_n, src.bit_sets,
+                        src.bit_rows, (uint32_t)n, src.max_len, c.pks.as<g1a>(), c.pre.as<int32_t>());
+  else if (src.com)  // cached committee sums minus the listed keys (the table is read as the registry is)
     launch_g1_committee_keys(st, reg, (uint32_t)g.reg_n, d.com.as<g1a>(), (uint32_t)g.com_n, src.com,
                              src.idx, src.off, (uint32_t)n, src.max_len, c.pks.as<g1a>(),
                              c.pre.as<int32_t>());
@@ -1330,10 +1353,67 @@ bool pipeline_verdicts(Ctx &c, Device &d, const uint8_t *msgs, const uint32_t *m
          pipeline_final(c.part.as<fp12>(), c.err.as<int32_t>(), 1, nseg, verdicts, st);
 }
 
-// Upload a HOST key source for sets [b, e) as a device key source.
-bool upload_pks(Ctx &c, const PkSource &host, size_t b, size_t e, hipStream_t st, PkSource *dev) {
+// Aggregation-bit sets [b, e) (gbls_bits.h): the plain sets' index lists, one BitSet per set
+// (a committee set's members resolved from Engine::mem to d's block memory; the caller holds the
+// registry lock) and this shard's slice of the bit strings, repacked to word-aligned rows.
+bool upload_bit_sets(Ctx &c, Device &d, const PkSource &host, size_t b, size_t e, hipStream_t st, PkSource *dev) {
+  const size_t n = e - b;
+  const uint32_t base = host.off ? host.off[b] : 0, cnt = host.off ? host.off[e] - base : 0;
+  if (!c.upload_staged(c.in2, cnt ? host.idx + base : nullptr, (size_t)cnt * 4, st)) return false;
+  size_t nw = 0;
+  for (size_t i = b; i < e; i++) nw += bits_row_words(host.bits_off[i + 1] - host.bits_off[i]);
+  // descriptors and rows are built in the call's pinned staging buffer itself: an epoch-sized call
+  // would pay more for fresh host vectors (page faults) and a second copy than for everything else
+  const size_t sets_bytes = n * sizeof(BitSet), rows_bytes = (nw + 1) * 4;
+  if (!c.ensure(c.in5, sets_bytes + 16) || !c.ensure(c.in7, rows_bytes + 16)) return false;
+  uint8_t *stage = static_cast<uint8_t *>(c.staging(sets_bytes + rows_bytes));
+  if (!stage) return fail(GBLS_ERR_HIP);
+  BitSet *sets = reinterpret_cast<BitSet *>(stage);
+  uint32_t *rows = reinterpret_cast<uint32_t *>(stage + sets_bytes);
+  rows[nw] = 0;
+  uint32_t w = 0;
+  for (size_t i = 0; i < n; i++) {
+    BitSet &s = sets[i];
+    s.slot = host.com[b + i];
+    s.list = nullptr;
+    s.cnt = s.row = s.nbytes = 0;
+    uint32_t work = 0;
+    if (s.slot == kNoCommittee) {
+      if (host.off) {
+        s.list = c.in2.as<uint32_t>() + (host.off[b + i] - base);
+        work = s.cnt = host.off[b + i + 1] - host.off[b + i];
+      }
+    } else {
+      const uint8_t *bits = host.bits + host.bits_off[b + i];
+      s.nbytes = host.bits_off[b + i + 1] - host.bits_off[b + i];
+      s.row = w;
+      bits_repack(&rows[w], bits, s.nbytes);
+      w += bits_row_words(s.nbytes);
+      const members::View v = s.slot < g.com_n ? g.mem.get(s.slot) : members::View();
+      if (v.block != members::kNoBlock) {
+        s.list = static_cast<const uint32_t *>(d.mem_blocks[v.block].p) + v.off;
+        s.cnt = v.len;
+        work = bits_work(&rows[s.row], s.nbytes, v.len);
+      }
+    }
+    dev->max_len = std::max(dev->max_len, work);
+  }
+  if (!c.send_staged(c.in5.p, sets, sets_bytes, st) || !c.send_staged(c.in7.p, rows, rows_bytes, st)) return false;
+  dev->idx = c.in2.as<uint32_t>();
+  dev->bit_sets = c.in5.p;
+  dev->bit_rows = c.in7.as<uint32_t>();
+  return true;
+}
+
+// Upload a HOST key source for sets [b, e) as a device key source (d: for aggregation-bit sets).
+bool upload_pks(Ctx &c, const PkSource &host, size_t b, size_t e, hipStream_t st, PkSource *dev,
+                Device *d = nullptr) {
   size_t n = e - b;
   *dev = PkSource();
+  if (host.bits_off) {
+    if (!host.com || !d) return fail(GBLS_ERR_ARG);
+    return upload_bit_sets(c, *d, host, b, e, st, dev);
+  }
   if (host.com) {  // committee slots per set, with index ranges (possibly all empty)
     if (!host.off) return fail(GBLS_ERR_ARG);
     uint32_t base = host.off[b], cnt = host.off[e] - base;
@@ -1480,7 +1560,7 @@ bool enqueue_host_batch(Ctx &c, Device &d, const uint8_t *msgs, const g2a *sigs,
     dsigs = c.in1.as<g2a>();
   }
   PkSource dsrc;
-  if (!upload_pks(c, src, b, e, st, &dsrc)) {
+  if (!upload_pks(c, src, b, e, st, &dsrc, &d)) {
     c.sig_c = nullptr;
     c.sig_st = nullptr;
     return false;
@@ -1720,6 +1800,19 @@ bool registry_streams(Device &d) {
   HIPCHK(hipEventCreateWithFlags(&d.reg_tmp, hipEventDisableTiming));
   return true;
 }
+// kept buffers of earlier retirements (no stream-ordered allocator) whose readers have finished
+void reap_kept(Device &d) {
+  for (size_t i = 0; i < d.reg_kept.size();) {
+    if (hipEventQuery(d.reg_kept[i].ev) == hipSuccess) {
+      (void)hipFree(d.reg_kept[i].p);
+      (void)hipEventDestroy(d.reg_kept[i].ev);
+      d.reg_kept.erase(d.reg_kept.begin() + (std::ptrdiff_t)i);
+    } else {
+      i++;
+    }
+  }
+  (void)hipGetLastError();
+}
 // Grow d's table to hold `need` bytes, stream-ordered on d.reg_st: a new table (zeroed past the
 // loaded entries, the loaded ones copied), and the old one freed on d.retire_st once the copy
 // and every kernel that read it have run (each context's last registry read, and the replica
@@ -1736,17 +1829,7 @@ bool table_grow(Device &d, Buf &tab, bool &tab_pooled, size_t need, size_t loade
   }
   if (loaded) HIPCHK(hipMemcpyAsync(nb, tab.p, loaded, hipMemcpyDeviceToDevice, d.reg_st));
   HIPCHK(hipMemsetAsync(static_cast<uint8_t *>(nb) + loaded, 0, want - loaded, d.reg_st));
-  // kept tables of earlier growths (no stream-ordered allocator) whose readers have finished
-  for (size_t i = 0; i < d.reg_kept.size();) {
-    if (hipEventQuery(d.reg_kept[i].ev) == hipSuccess) {
-      (void)hipFree(d.reg_kept[i].p);
-      (void)hipEventDestroy(d.reg_kept[i].ev);
-      d.reg_kept.erase(d.reg_kept.begin() + (std::ptrdiff_t)i);
-    } else {
-      i++;
-    }
-  }
-  (void)hipGetLastError();
+  reap_kept(d);
   if (tab.p) {
     // the retire stream is created by the first growth that retires a table (a stream holds a
     // hardware queue from its creation; the engine's queue set is tuned, see kPrewarmCtx)
@@ -1785,6 +1868,56 @@ bool table_wait_readers(Device &d) {
     if (c.reg_read && hipStreamWaitEvent(d.reg_st, c.ev_reg, 0) != hipSuccess) ok = false;
   });
   return ok || fail(GBLS_ERR_HIP);
+}
+// ---- resident member lists (gbls_members.h): the device memory of the blocks.  Under reg_mu held
+// exclusively, like every table write.
+// A block of `bytes` on d, allocated and filled from `host` on d.reg_st (staged through c).
+bool block_upload(Ctx &c, Device &d, uint32_t id, const void *host, size_t bytes) {
+  if (d.mem_blocks.size() <= id) d.mem_blocks.resize(id + 1);
+  Device::MemBlock &mb = d.mem_blocks[id];
+  mb.pooled = true;
+  if (hipMallocAsync(&mb.p, bytes + 16, d.reg_st) != hipSuccess) {  // no stream-ordered allocator
+    (void)hipGetLastError();
+    mb.pooled = false;
+    mb.p = nullptr;
+    HIPCHK(hipMalloc(&mb.p, bytes + 16));
+  }
+  return c.upload_to(mb.p, host, bytes, d.reg_st);
+}
+// Free d's memory of a dead block behind the work that may still read it: what d.reg_st holds (the
+// call that summed it) and every kernel enqueued by a reader (each context's last registry read:
+// readers enqueue under the shared lock, so all of them precede this write).  On the retire
+// stream; no host wait, no device synchronisation.
+bool block_retire(Device &d, Device::MemBlock &mb) {
+  void *p = mb.p;
+  const bool pooled = mb.pooled;
+  mb = Device::MemBlock();
+  if (!p) return true;
+  HIPCHK(hipSetDevice(d.hipdev));
+  if (!d.retire_st) HIPCHK(hipStreamCreateWithFlags(&d.retire_st, hipStreamNonBlocking));
+  HIPCHK(hipEventRecord(d.reg_tmp, d.reg_st));
+  HIPCHK(hipStreamWaitEvent(d.retire_st, d.reg_tmp, 0));
+  bool ok = true;
+  d.pool.for_each([&](Ctx &c) {
+    if (c.reg_read && hipStreamWaitEvent(d.retire_st, c.ev_reg, 0) != hipSuccess) ok = false;
+  });
+  if (!ok) return fail(GBLS_ERR_HIP);  // (the block is leaked rather than freed under a reader)
+  if (pooled) {
+    HIPCHK(hipFreeAsync(p, d.retire_st));
+  } else {
+    reap_kept(d);
+    Device::Kept k{p, nullptr};
+    HIPCHK(hipEventCreateWithFlags(&k.ev, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(k.ev, d.retire_st));
+    d.reg_kept.push_back(k);
+  }
+  return true;
+}
+// the blocks that lost their last slot since the last call, on every device
+void members_reap() {
+  for (uint32_t b : g.mem.take_dead())
+    for (auto &dp : g.devs)
+      if (b < dp->mem_blocks.size()) (void)block_retire(*dp, dp->mem_blocks[b]);
 }
 // a block import in progress: normal submissions keep off the reserved CUs meanwhile
 struct BlockActive {
@@ -2386,7 +2519,11 @@ int gbls_registry_set(size_t first, const uint8_t (*pks)[48], size_t n, int32_t 
   std::unique_lock<std::shared_mutex> wl(g.reg_mu);
   {
     // loaded keys are rewritten: the cached committee sums are snapshots of them, all dropped
-    if (first < g.reg_n) g.com_n = 0;
+    if (first < g.reg_n) {
+      g.com_n = 0;
+      g.mem.drop_from(0);
+      members_reap();
+    }
     new_n = std::max(g.reg_n, first + n);
     if (new_n > 0xffffffffull) return fail(GBLS_ERR_ARG), FAILED;
     Device &d0 = *g.devs[0];
@@ -2471,8 +2608,11 @@ size_t gbls_registry_size(void) {
 // committees from ITS OWN registry replica (launch_g1_aggregate_idx writing at the slot offset):
 // the devices work side by side, so n devices cost the wall time of one, with no peer copy and no
 // cross-device event; the index lists (4 bytes per member) are uploaded once per device.
-int gbls_committees_set(size_t first, const uint32_t *idx, const uint32_t *off, size_t ncom,
-                        int32_t *status) {
+// keep: the slots also keep their member lists (gbls_committees_set_members): the call's indices
+// become one block per device, which the sums are then formed from; else the slots' members, if
+// any, are dropped.
+static int committees_set_impl(size_t first, const uint32_t *idx, const uint32_t *off, size_t ncom,
+                               int32_t *status, bool keep) {
   fill(status, ncom, GBLS_BAD_ENCODING);
   API_BEGIN
   if (first > kMaxCommittees || ncom > kMaxCommittees - first) return fail(GBLS_ERR_ARG), FAILED;
@@ -2488,17 +2628,28 @@ int gbls_committees_set(size_t first, const uint32_t *idx, const uint32_t *off, 
     }
   } guard{done};
   size_t new_n = 0;  // the size this call commits
+  uint32_t blk = members::kNoBlock;  // this call's member block (keep)
+  uint64_t blk_serial = 0;
   // a failure truncates the table to `first` (after the lock was released only while no later
   // call has moved the size on from this call's)
   auto broken = [&](std::unique_lock<std::shared_mutex> &wl) {
     const bool relock = !wl.owns_lock();
     if (relock) wl.lock();
-    if (!relock || g.com_n == new_n) g.com_n = std::min(g.com_n, first);
+    if (!relock && blk != members::kNoBlock) g.mem.close_block(blk);  // no slot assigned yet: it dies
+    if (!relock || g.com_n == new_n) {
+      g.com_n = std::min(g.com_n, first);
+      g.mem.drop_from(first);
+    }
+    members_reap();
     fill(status, ncom, GBLS_BAD_ENCODING);
     return FAILED;
   };
   std::unique_lock<std::shared_mutex> wl(g.reg_mu);
   new_n = std::max(g.com_n, first + ncom);
+  if (keep && ncom) {
+    blk = g.mem.open_block(nidx);
+    blk_serial = g.mem.serial(blk);
+  }
   for (auto &dp : g.devs) {
     Device &d = *dp;
     if (!registry_streams(d) || hipSetDevice(d.hipdev) != hipSuccess) return fail(GBLS_ERR_HIP), broken(wl);
@@ -2516,10 +2667,12 @@ int gbls_committees_set(size_t first, const uint32_t *idx, const uint32_t *off, 
       Lease L(d);  // workspaces and staging; the work itself runs on the registry stream
       Ctx &c = *L;
       hipStream_t st = d.reg_st;
-      if (!L.ok() || !c.begin(st) || !c.upload_staged(c.in0, idx, nidx * 4, st) ||
+      if (!L.ok() || !c.begin(st) ||
+          !(keep ? block_upload(c, d, blk, idx, nidx * 4) : c.upload_staged(c.in0, idx, nidx * 4, st)) ||
           !c.upload_staged(c.in1, off, (ncom + 1) * 4, st) || !c.ensure(c.out1, ncom * sizeof(int32_t)))
         return broken(wl);
-      launch_g1_aggregate_idx(st, d.reg.as<g1a>(), (uint32_t)g.reg_n, c.in0.as<uint32_t>(),
+      const uint32_t *didx = keep ? static_cast<const uint32_t *>(d.mem_blocks[blk].p) : c.in0.as<uint32_t>();
+      launch_g1_aggregate_idx(st, d.reg.as<g1a>(), (uint32_t)g.reg_n, didx,
                               c.in1.as<uint32_t>(), (uint32_t)ncom, d.com.as<g1a>() + first,
                               c.out1.as<int32_t>());
       if (&d == g.devs[0].get() &&  // the statuses are the same on every replica
@@ -2536,11 +2689,34 @@ int gbls_committees_set(size_t first, const uint32_t *idx, const uint32_t *off, 
     d.reg_ev_set = true;
   }
   g.com_n = new_n;
+  // the slots' views move to this call's block (or to none); blocks that lost their last slot
+  // are freed behind their readers
+  for (size_t c = 0; c < ncom; c++) {
+    if (keep)
+      g.mem.assign(first + c, blk, off[c], off[c + 1] - off[c]);
+    else
+      g.mem.drop(first + c);
+  }
+  if (blk != members::kNoBlock) g.mem.close_block(blk);
+  members_reap();
   wl.unlock();
   for (hipEvent_t e : done)
     if (hipEventSynchronize(e) != hipSuccess) return fail(GBLS_ERR_HIP), broken(wl);
   if (ncom) std::memcpy(status, st0.data(), ncom * 4);
+  bool rejected = false;
+  for (size_t c = 0; keep && c < ncom; c++) rejected |= st0[c] != GBLS_SUCCESS;
+  if (rejected) {  // a slot whose status is not GBLS_SUCCESS keeps no members (its sum is all-zero:
+    wl.lock();     // a reader that came in between has rejected it all the same)
+    for (size_t c = 0; c < ncom; c++)
+      if (st0[c] != GBLS_SUCCESS) g.mem.drop_if(first + c, blk, blk_serial);
+    members_reap();
+  }
   return GBLS_SUCCESS;
+}
+
+int gbls_committees_set(size_t first, const uint32_t *idx, const uint32_t *off, size_t ncom,
+                        int32_t *status) {
+  return committees_set_impl(first, idx, off, ncom, status, false);
 }
 
 size_t gbls_committees_size(void) {
@@ -2552,6 +2728,8 @@ int gbls_committees_clear(void) {
   API_BEGIN
   std::unique_lock<std::shared_mutex> wl(g.reg_mu);
   g.com_n = 0;
+  g.mem.drop_from(0);
+  members_reap();
   return GBLS_SUCCESS;
 }
 
@@ -2614,6 +2792,101 @@ int gbls_multi_verify_committees(const uint8_t (*msgs)[32], const uint8_t (*sigs
   const int cls = (call_flags & GBLS_CALL_BLOCK) ? 1 : 0;
   BlockActive block_active(cls != 0);
   // its own submission (not queued with the coalescer's requests, which do not carry committees)
+  if (!verify_host(&msgs[0][0], nullptr, &sigs[0][0], sig_status, src, rands, n, off, 1, &v, cls)) {
+    fill(sig_status, n, GBLS_BAD_ENCODING);
+    return GBLS_VERIFY_FAIL;
+  }
+  for (size_t i = 0; i < n; i++)  // MultiVerifier::finish: a decoding error comes first
+    if (sig_status[i] != GBLS_SUCCESS) return sig_status[i];
+  return v;
+}
+
+// ---- aggregation-bit sets (include/grandine_bls_gpu_bits.h): committee slots with resident member
+// lists (gbls_members.h for the bookkeeping, the blocks' device memory above), sets given as a
+// slot and the attestation's own bits, keys chosen on the device (k_bits.hip).
+int gbls_committees_set_members(size_t first, const uint32_t *idx, const uint32_t *off, size_t ncom,
+                                int32_t *status) {
+  return committees_set_impl(first, idx, off, ncom, status, true);
+}
+
+size_t gbls_committees_members(size_t slot) {
+  if (!g.ready.load()) return 0;
+  std::shared_lock<std::shared_mutex> rl(g.reg_mu);
+  return slot < g.com_n ? g.mem.count(slot) : 0;
+}
+
+// the arguments of an aggregation-bit key source (both calls below): a committee set has no index
+// range, a plain set no bits
+static bool bits_args_ok(const uint32_t *com, const uint8_t *bits, const uint32_t *bits_off,
+                         const uint32_t *pk_idx, const uint32_t *pk_off, size_t n) {
+  if (!com || !bits_off || n > 0xfffffffeull || !valid_offsets(bits_off, n, bits_off[n])) return false;
+  if (pk_off && !valid_offsets(pk_off, n, pk_off[n])) return false;
+  if ((bits_off[n] && !bits) || (pk_off && pk_off[n] && !pk_idx)) return false;
+  for (size_t i = 0; i < n; i++) {
+    const bool plain = com[i] == GBLS_NO_COMMITTEE;
+    if (plain ? bits_off[i + 1] != bits_off[i] : (pk_off && pk_off[i + 1] != pk_off[i])) return false;
+  }
+  return true;
+}
+
+int gbls_g1_aggregate_bits(const uint32_t *com, const uint8_t *bits, const uint32_t *bits_off,
+                           const uint32_t *pk_idx, const uint32_t *pk_off, size_t n, gbls_p1_affine *out,
+                           int32_t *status) {
+  fill(status, n, GBLS_BAD_ENCODING);
+  if (out) std::memset(out, 0, n * sizeof(*out));
+  API_BEGIN
+  if (n == 0) return GBLS_SUCCESS;
+  if (!out || !bits_args_ok(com, bits, bits_off, pk_idx, pk_off, n)) return fail(GBLS_ERR_ARG), FAILED;
+  PkSource src, dsrc;
+  src.com = com;
+  src.bits = bits;
+  src.bits_off = bits_off;
+  src.idx = pk_idx;
+  src.off = pk_off;
+  std::shared_lock<std::shared_mutex> rl(g.reg_mu);
+  Device &d = pick_device();
+  Lease L(d);
+  Ctx &c = *L;
+  hipStream_t st = c.own;
+  const g1a *keys = nullptr;
+  const int32_t *pre = nullptr;
+  if (!L.ok() || !c.begin(st) || !upload_pks(c, src, 0, n, st, &dsrc, &d) ||
+      !resolve_pks(c, d, dsrc, n, st, &keys, &pre))
+    return FAILED;
+  if (hipMemcpyAsync(out, keys, n * sizeof(g1a), hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipMemcpyAsync(status, pre, n * 4, hipMemcpyDeviceToHost, st) != hipSuccess)
+    return fail(GBLS_ERR_HIP), FAILED;
+  rl.unlock();  // enqueued: the host wait below does not hold up registry updates
+  if (hipStreamSynchronize(st) != hipSuccess) {
+    fill(status, n, GBLS_BAD_ENCODING);
+    std::memset(out, 0, n * sizeof(*out));
+    return fail(GBLS_ERR_HIP), FAILED;
+  }
+  return GBLS_SUCCESS;
+}
+
+int gbls_multi_verify_bits(const uint8_t (*msgs)[32], const uint8_t (*sigs)[96], const uint32_t *com,
+                           const uint8_t *bits, const uint32_t *bits_off, const uint32_t *pk_idx,
+                           const uint32_t *pk_off, const uint64_t *rands, size_t n, int32_t *sig_status,
+                           uint32_t call_flags) {
+  t_last_error = GBLS_ERR_NONE;
+  if (!sig_status) return fail(GBLS_ERR_ARG), GBLS_VERIFY_FAIL;
+  fill(sig_status, n, GBLS_BAD_ENCODING);
+  API_BEGIN
+  if (n == 0) return GBLS_VERIFY_FAIL;
+  if (!msgs || !sigs || !rands || !bits_args_ok(com, bits, bits_off, pk_idx, pk_off, n))
+    return fail(GBLS_ERR_ARG), GBLS_VERIFY_FAIL;
+  PkSource src;
+  src.com = com;
+  src.bits = bits;
+  src.bits_off = bits_off;
+  src.idx = pk_idx;
+  src.off = pk_off;
+  uint32_t off[2] = {0, (uint32_t)n};
+  int32_t v = GBLS_VERIFY_FAIL;
+  const int cls = (call_flags & GBLS_CALL_BLOCK) ? 1 : 0;
+  BlockActive block_active(cls != 0);
+  // its own submission, as the committees call (the coalescer's requests carry neither)
   if (!verify_host(&msgs[0][0], nullptr, &sigs[0][0], sig_status, src, rands, n, off, 1, &v, cls)) {
     fill(sig_status, n, GBLS_BAD_ENCODING);
     return GBLS_VERIFY_FAIL;

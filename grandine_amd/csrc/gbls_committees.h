@@ -21,6 +21,13 @@ enum : uint32_t {
   CK_BAD_INDEX = 4,  // a listed index is past the registry or names an invalid / unloaded key
 };
 
+// The direction of a set whose participants are known (aggregation bits, gbls_bits.h): with p of a
+// committee's m members participating, the key is formed as C minus the m - p absentees when those
+// are the fewer, else as the participants' sum; a tie goes to the participants (the measured rule of
+// the committees call, verifier.ABSENTEE_FORM_MAX_RATIO = 1).  p == m subtracts nothing: the key
+// is C itself.
+HD bool committee_subtracts(uint32_t m, uint32_t p) { return m - p < p; }
+
 // key = C - S (CK_COMMITTEE) or S; returns the set's status and writes all-zero on a rejection.
 //   BAD_ENCODING        a bad index, or a committee slot that is invalid (all-zero: never written,
 //                       written with a nonzero status, an infinite sum) or past the table

@@ -96,6 +96,13 @@ extern uint32_t g_committee_row_min;
 void launch_g1_committee_keys(hipStream_t st, const g1a *reg, uint32_t nreg, const g1a *tab, uint32_t ntab,
                               const uint32_t *com, const uint32_t *idx, const uint32_t *off, uint32_t n,
                               uint32_t max_len, g1a *out, int32_t *status);
+// k_bits.hip -- keys from aggregation bits over resident committee members: sets = n BitSet
+// descriptors, rows = their repacked bit strings (gbls_bits.h).  max_work: the longest set's work
+// (the keys its longest lane chain adds: min(participants, absentees) of a committee set, a plain
+// set's list), which picks the launch form by the same g_committee_row_min
+void launch_g1_bits_keys(hipStream_t st, const g1a *reg, uint32_t nreg, const g1a *tab, uint32_t ntab,
+                         const void *sets, const uint32_t *rows, uint32_t n, uint32_t max_work, g1a *out,
+                         int32_t *status);
 void launch_sk_to_pk(hipStream_t st, const uint8_t *sks, uint32_t n, g1a *out);
 void launch_sign(hipStream_t st, const uint8_t *sks, const g2a *H, uint32_t n, g2a *out);
 void launch_mad_peak(hipStream_t st, unsigned blocks, uint64_t *sink, uint32_t iters, uint32_t seed);

@@ -121,6 +121,14 @@ struct KeySource {
   // coalescer (Request::kind does not know it): such a call is its own submission.
   const uint32_t *com = nullptr;
   uint32_t max_len = 0;           // ... and the longest range (a device source: the launch form)
+  // aggregation-bit sets (with com; gbls_bits.h): a committee set's key is the sum of the slot's
+  // resident members whose bit is set, the other sets sum their idx range (off may be nullptr
+  // when there is none).  Host source: the bit strings and their byte offsets.  Device source:
+  // the BitSet descriptors and the repacked bit rows; max_len is then the longest set's work.
+  const uint8_t *bits = nullptr;
+  const uint32_t *bits_off = nullptr;
+  const void *bit_sets = nullptr;
+  const uint32_t *bit_rows = nullptr;
 };
 
 // One caller's batch (host pointers, borrowed for the call).  rands == nullptr: independent

@@ -64,7 +64,7 @@ class Triple:
     ``verify_aggregate``, the message, signature and the KEY LIST whose sum is the key."""
 
     IS_NULL = False
-    __slots__ = ("message", "signature_bytes", "_key", "deferred", "indices", "slot", "committee", "absent")
+    __slots__ = ("message", "signature_bytes", "_key", "deferred", "indices", "slot", "committee", "absent", "bits")
 
     def __init__(self, message: bytes = bytes(32), signature_bytes: bytes = None,
                  public_key: "bls.PublicKey" = None):
@@ -76,6 +76,7 @@ class Triple:
         self.slot = None      # the committee table slot (verify_aggregate_committee), with
         self.committee = None  # ... the committee's member indices
         self.absent = None    # ... and the members whose aggregation bit is clear
+        self.bits = None      # ... and the aggregation bits as SSZ bytes
 
     def verify_aggregate(self, message, signature_bytes, public_keys, signature_kind=None):
         """verifier.rs:387-405 without the reduce: the keys are kept and summed on the device by
@@ -88,7 +89,7 @@ class Triple:
         # a reused triple keeps nothing of its previous set (rust/bls_patch/verifier.rs resets
         # its indices the same way)
         self.indices = None
-        self.slot = self.committee = self.absent = None
+        self.slot = self.committee = self.absent = self.bits = None
 
     def verify_aggregate_indexed(self, message, signature_bytes, validator_indices, public_keys,
                                  signature_kind=None):
@@ -104,16 +105,30 @@ class Triple:
         slot ``slot`` (bls.Committees), ``aggregation_bits`` selects the participants and
         ``public_keys`` are the participants' keys.  Keeps the participants' indices, as
         verify_aggregate_indexed does, plus the slot, the committee and the absentees, so that
-        MultiVerifier.finish can send whichever list is shorter."""
+        MultiVerifier.finish can send whichever list is shorter, and the bits themselves for a slot
+        whose members are resident: ``bytes`` are taken as the SSZ encoding (a Bitlist with its
+        delimiter or a Bitvector) and passed through, a sequence of bools is packed as a
+        Bitvector."""
         committee = [int(i) for i in committee]
-        bits = [bool(b) for b in aggregation_bits]
-        if len(bits) != len(committee):
-            raise ValueError("one aggregation bit per committee member")
+        if isinstance(aggregation_bits, (bytes, bytearray)):
+            raw = bytes(aggregation_bits)
+            if len(raw) < (len(committee) + 7) // 8:
+                raise ValueError("one aggregation bit per committee member")
+            bits = [bool(raw[j >> 3] >> (j & 7) & 1) for j in range(len(committee))]
+        else:
+            bits = [bool(b) for b in aggregation_bits]
+            if len(bits) != len(committee):
+                raise ValueError("one aggregation bit per committee member")
+            packed = bytearray((len(bits) + 7) // 8)
+            for j, b in enumerate(bits):
+                packed[j >> 3] |= int(b) << (j & 7)
+            raw = bytes(packed)
         self.verify_aggregate_indexed(message, signature_bytes, [v for v, b in zip(committee, bits) if b],
                                       public_keys, signature_kind)
         self.slot = int(slot)
         self.committee = committee
         self.absent = [v for v, b in zip(committee, bits) if not b]
+        self.bits = raw
 
     @property
     def public_key(self) -> "bls.PublicKey":
@@ -213,7 +228,7 @@ class MultiVerifier(Verifier):
     def __init__(self, options: Iterable[VerifierOption] = (), triples: Optional[List[Triple]] = None):
         self.triples: List[Triple] = list(triples or [])
         self.options = set(options)
-        self.last_path = None  # "committees", "indices" or "points": the key form of the last finish (tests)
+        self.last_path = None  # "bits", "committees", "indices" or "points": the key form of the last finish (tests)
 
     @classmethod
     def from_triples(cls, triples: List[Triple]) -> "MultiVerifier":  # From<Vec<Triple>>
@@ -256,7 +271,17 @@ class MultiVerifier(Verifier):
         sigs = [t.signature_bytes for t in self.triples]
         indexed = all(t.indices is not None and bls.Registry.covers(t.indices) for t in self.triples)
         com = [t for t in self.triples if t.slot is not None]
-        if indexed and com and all(bls.Committees.covers(t.slot, t.committee) and bls.Registry.covers(t.absent)
+        if com and all(bls.Committees.has_members(t.slot) and bls.Committees.covers(t.slot, t.committee)
+                       for t in com) and all(t.indices is not None and bls.Registry.covers(t.indices)
+                                             for t in self.triples if t.slot is None):
+            # resident members: a committee triple is its slot and its aggregation bits as they
+            # arrived (the engine checks them against the committee and picks the direction), the
+            # other triples their registry indices
+            self.last_path = "bits"
+            rc = bls.Signature.multi_verify_compressed_bits(
+                msgs, sigs, [t.slot for t in self.triples], [t.bits if t.slot is not None else b"" for t in self.triples],
+                [() if t.slot is not None else t.indices for t in self.triples], randoms, flags)
+        elif indexed and com and all(bls.Committees.covers(t.slot, t.committee) and bls.Registry.covers(t.absent)
                                    for t in com):
             # cached committee sums: per committee triple the absentees (key = slot - their sum)
             # or, when they are the longer list, the participants without a slot

@@ -20,8 +20,10 @@
 //!   the point.  No `transmute`, no reliance on the private layout of blst's wrapper types.
 #![deny(unsafe_op_in_unsafe_fn)]
 
+pub mod bits;
 pub mod committees;
 pub mod ffi;
+pub mod ffi_bits;
 pub mod ffi_committees;
 pub mod ffi_msgcache;
 pub mod msgcache;

@@ -17,7 +17,17 @@ gbls_committees_set for the shape's committees (the one-off cost per epoch), and
 key resolution alone (gbls_g1_aggregate_committees), which is what the launch-form switch
 (GBLS_COMMITTEE_ROW_MIN, with --tuning) moves.
 
+With --bits the table is loaded with gbls_committees_set_members and the same sets also go through
+the aggregation-bit calls (include/grandine_bls_gpu_bits.h), a slot and an SSZ Bitlist per set:
+
+  bits          gbls_multi_verify_bits
+  keys_bits     gbls_g1_aggregate_bits (beside keys_absentees / keys_participants)
+
+alternating with the two committees forms (the yardstick of that leg; `parent` is left out), and
+each result carries the host bytes a call uploads for its key source (upload_bytes).
+
   python tools/bench_committees.py                       # both shapes, one JSON line per point
+  python tools/bench_committees.py --bits                # ... the aggregation-bit leg
   GBLS_COMMITTEE_ROW_MIN=1 python tools/bench_committees.py --tuning --keys-only
 """
 import argparse
@@ -65,6 +75,8 @@ def main():
     ap.add_argument("--absent", default="", help="comma-separated absentee counts (default: %s)" % ABSENT)
     ap.add_argument("--keys", action="store_true", help="also time the key resolution alone")
     ap.add_argument("--keys-only", action="store_true", help="only the key resolution")
+    ap.add_argument("--bits", action="store_true",
+                    help="the aggregation-bit calls beside the two committees forms, full calls and keys alone")
     ap.add_argument("--out", default="", help="also append the JSON lines to this file")
     ap.add_argument("--tuning", action="store_true", help="let the engine read its GBLS_* tuning variables")
     a = ap.parse_args()
@@ -98,11 +110,12 @@ def main():
 
         def set_table():
             t0 = time.perf_counter()
-            rc = L.gbls_committees_set(0, perm_c.ctypes.data_as(ctypes.c_void_p), off_c.ctypes.data_as(ctypes.c_void_p),
+            load = L.gbls_committees_set_members if a.bits else L.gbls_committees_set
+            rc = load(0, perm_c.ctypes.data_as(ctypes.c_void_p), off_c.ctypes.data_as(ctypes.c_void_p),
                                        ncom, st)
             dt = time.perf_counter() - t0
             if rc != G.SUCCESS or any(st[c] for c in range(ncom)):
-                raise SystemExit("%s: gbls_committees_set rc=%d" % (name, rc))
+                raise SystemExit("%s: %s rc=%d" % (name, "gbls_committees_set_members" if a.bits else "gbls_committees_set", rc))
             return dt
 
         f, calls = timed(lambda k: set_table(), ["set"], 2, a.window, a.runs)
@@ -134,6 +147,20 @@ def main():
             none = np.full(ncom, G.NO_COMMITTEE, dtype=np.uint32)
             ptr = lambda x: x.ctypes.data_as(ctypes.c_void_p)
             keys_out = ctypes.create_string_buffer(96 * ncom)
+            # an attestation's aggregation_bits per set: a Bitlist over the committee, the first k clear
+            fields = []
+            for c in range(ncom):
+                m = int(off[c + 1] - off[c])
+                bits = np.zeros(8 * (m // 8 + 1), dtype=np.uint8)
+                bits[k:m] = 1
+                bits[m] = 1  # the delimiter
+                fields.append(np.packbits(bits, bitorder="little").tobytes())
+            b_all = ctypes.create_string_buffer(b"".join(fields), sum(len(x) for x in fields))
+            b_off = np.zeros(ncom + 1, dtype=np.uint32)
+            b_off[1:] = np.cumsum([len(x) for x in fields])
+            upload = {"absentees": 4 * ncom + 4 * (ncom + 1) + 4 * int(a_off[ncom]),
+                      "participants": 4 * ncom + 4 * (ncom + 1) + 4 * int(p_off[ncom]),
+                      "bits": 4 * ncom + 4 * (ncom + 1) + int(b_off[ncom])}
 
             def call(which):
                 t0 = time.perf_counter()
@@ -146,6 +173,11 @@ def main():
                 elif which == "participants":
                     rc = L.gbls_multi_verify_committees(msgs, sig_c, ptr(none), ptr(p_idx), ptr(p_off), rands, ncom,
                                                         sig_st, 0)
+                elif which == "bits":
+                    rc = L.gbls_multi_verify_bits(msgs, sig_c, ptr(slots), b_all, ptr(b_off), None, None, rands, ncom,
+                                                  sig_st, 0)
+                elif which == "keys_bits":
+                    rc = L.gbls_g1_aggregate_bits(ptr(slots), b_all, ptr(b_off), None, None, ncom, keys_out, sig_st)
                 elif which == "keys_absentees":
                     rc = L.gbls_g1_aggregate_committees(ptr(slots), ptr(a_idx), ptr(a_off), ncom, keys_out, sig_st)
                 else:
@@ -158,8 +190,13 @@ def main():
             kinds = [] if a.keys_only else ["parent", "absentees", "participants"]
             if a.keys or a.keys_only:
                 kinds += ["keys_absentees", "keys_participants"]
+            if a.bits:
+                kinds = ([] if a.keys_only else ["absentees", "participants", "bits"]) + [
+                    "keys_absentees", "keys_participants", "keys_bits"]
             f, calls = timed(call, kinds, a.warmup, a.window, a.runs)
             res = {"shape": name, "sets": ncom, "absent": k, "calls_per_run": calls}
+            if a.bits:
+                res["upload_bytes"] = upload
             for kind in kinds:
                 res[kind] = summary(f[kind])
                 res[kind]["runs_us"] = [round(x, 1) for x in f[kind]]
