@@ -380,6 +380,42 @@ class Signature:
             G.u32_array(boff), G.u32_array(flat or [0]), G.u32_array(off), G.u64_array(randoms), n, st, call_flags)
 
     @staticmethod
+    def multi_verify_compressed_spans(messages: Iterable[bytes], signature_bytes: Iterable[bytes],
+                                      base_slots: Iterable[int], committee_bits: Iterable[bytes],
+                                      bitfields: Iterable[bytes], validator_indices: Iterable[Sequence[int]],
+                                      randoms: Sequence[int] = None, call_flags: int = 0) -> int:
+        """multi_verify_compressed_bits for attestations over several committees
+        (gbls_multi_verify_spans): set i names the committees ``base_slots[i] + c`` for every set
+        bit c of ``committee_bits[i]`` (8 SSZ bytes), each loaded with its members, and carries ONE
+        bit string ``bitfields[i]`` over their concatenation.  A set whose base slot is ``None`` is
+        the plain sum of the registry keys ``validator_indices[i]``, with neither mask nor bits.
+        Returns as multi_verify_compressed."""
+        msgs = [bytes(m) for m in messages]
+        sigs = [bytes(s) for s in signature_bytes]
+        com = [G.NO_COMMITTEE if c is None else int(c) for c in base_slots]
+        masks = [bytes(b or bytes(8)) for b in committee_bits]
+        fields = [bytes(b or b"") for b in bitfields]
+        idx = [list(v or ()) for v in validator_indices]
+        n = len(sigs)
+        if n == 0 or len(msgs) != n or len(idx) != n or len(com) != n or len(fields) != n or len(masks) != n:
+            return G.VERIFY_FAIL
+        if any(len(m) != 32 for m in msgs) or any(len(s) != 96 for s in sigs) or any(len(b) != 8 for b in masks):
+            raise ValueError("messages must be 32-byte signing roots, signatures 96 bytes, committee_bits 8 bytes")
+        if randoms is None:
+            randoms = [secrets.randbits(64) or 1 for _ in range(n)]
+        off, boff = [0], [0]
+        for v, b in zip(idx, fields):
+            off.append(off[-1] + len(v))
+            boff.append(boff[-1] + len(b))
+        flat = [i for v in idx for i in v]
+        L = G.lib()
+        st = G.i32_array(n)
+        return L.gbls_multi_verify_spans(
+            G.buf(b"".join(msgs)), G.buf(b"".join(sigs)), G.u32_array(com), G.buf(b"".join(masks)),
+            G.buf(b"".join(fields)), G.u32_array(boff), G.u32_array(flat or [0]), G.u32_array(off),
+            G.u64_array(randoms), n, st, call_flags)
+
+    @staticmethod
     def verify_batch_compressed(messages: Iterable[bytes], signature_bytes: Iterable[bytes],
                                 public_keys: Iterable) -> List:
         """SingleVerifier::extend's try_from + verify per triple (verifier.rs:215-236) as ONE

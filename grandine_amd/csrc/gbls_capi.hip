@@ -37,6 +37,7 @@
 #include "../../include/grandine_bls_gpu_committees.h"
 #include "../../include/grandine_bls_gpu_msgcache.h"
 #include "../../include/grandine_bls_gpu_bits.h"
+#include "../../include/grandine_bls_gpu_spans.h"
 #include "gbls_common.h"
 #include "gbls_bits.h"
 #include "gbls_committees.h"
@@ -44,6 +45,7 @@
 #include "gbls_members.h"
 #include "gbls_msgcache.h"
 #include "gbls_sched.h"
+#include "gbls_spans.h"
 #include "gbls_tables.h"
 
 using namespace gbls;
@@ -252,7 +254,7 @@ struct Ctx {
   bool used = false;                  // last_stream is meaningful
   hipStream_t last_stream = nullptr;  // main stream of the previous call
   Buf in0, in1, in2, in3, in4, in5, U, Q, H, P, Pc, R, Sj, gpart, lines, Ts, V0, V1, V28, hparts, tab, part, err, out0,
-      out1, pks, pre, pre2, msm, sigd, sigst, rnd, ng1, gerr, gv, redo, rtab, in6, Pset, in7;
+      out1, pks, pre, pre2, msm, sigd, sigst, rnd, ng1, gerr, gv, redo, rtab, in6, Pset, in7, in8, spj, spf;
   // per-call option of the next pipeline_partials on this lease: compressed signatures
   // (96 B each, device) to decompress on the signature-side stream into `sigs`, with their
   // BLST_ERROR statuses (device) failing their segments (consumed and reset by the pipeline)
@@ -843,7 +845,13 @@ bool resolve_pks(Ctx &c, Device &d, const PkSource &src, size_t n, hipStream_t s
   StageTimer t(S_PK_GATHER, st);
   const g1a *reg = d.reg.as<g1a>();
   if (src.idx && !registry_read_begin(c, d, st)) return false;
-  if (src.bit_sets)  // resident members chosen by aggregation bits (member blocks: read as the registry is)
+  if (src.span_sets) {  // span sets: a contribution per (set, committee) piece, folded per set (k_spans.hip)
+    const size_t np = src.span_np;
+    if (!c.ensure(c.spj, np * sizeof(g1j) + 16) || !c.ensure(c.spf, np * 4 + 16)) return false;
+    launch_g1_span_keys(st, reg, (uint32_t)g.reg_n, d.com.as<g1a>(), (uint32_t)g.com_n, src.span_pieces,
+                        src.span_sets, src.bit_rows, src.span_np, (uint32_t)n, src.max_len, src.span_max_pieces,
+                        c.spj.p, c.spf.as<uint32_t>(), c.pks.as<g1a>(), c.pre.as<int32_t>());
+  } else if (src.bit_sets)  // resident members chosen by aggregation bits (member blocks: read as the registry is)
     launch_g1_bits_keys(st, reg, (uint32_t)g.reg_n, d.com.as<g1a>(), (uint32_t)g.com_n, src.bit_sets,
                         src.bit_rows, (uint32_t)n, src.max_len, c.pks.as<g1a>(), c.pre.as<int32_t>());
   else if (src.com)  // cached committee sums minus the listed keys (the table is read as the registry is)
@@ -1405,6 +1413,77 @@ bool upload_bit_sets(Ctx &c, Device &d, const PkSource &host, size_t b, size_t e
   return true;
 }
 
+// Span sets [b, e) (gbls_spans.h): the plain sets' index lists, one SpanSet per set, one SpanPiece
+// per (set, named committee) pair or plain list (members resolved from Engine::mem to d's block
+// memory; the caller holds the registry lock) and this shard's slice of the bit strings, repacked
+// to word-aligned rows.  The call's piece count fits 32 bits (spans_args_ok).
+bool upload_span_sets(Ctx &c, Device &d, const PkSource &host, size_t b, size_t e, hipStream_t st, PkSource *dev) {
+  const size_t n = e - b;
+  const uint32_t base = host.off ? host.off[b] : 0, cnt = host.off ? host.off[e] - base : 0;
+  if (!c.upload_staged(c.in2, cnt ? host.idx + base : nullptr, (size_t)cnt * 4, st)) return false;
+  size_t nw = 0, np = 0;
+  for (size_t i = b; i < e; i++) {
+    nw += bits_row_words(host.bits_off[i + 1] - host.bits_off[i]);
+    np += host.com[i] == kNoCommittee ? 1 : span_mask_count(host.cbits[i]);
+  }
+  // built in the call's pinned staging buffer itself, as upload_bit_sets does
+  const size_t sets_bytes = (n * sizeof(SpanSet) + 7) & ~(size_t)7, pieces_bytes = np * sizeof(SpanPiece),
+               rows_bytes = (nw + 1) * 4;
+  if (!c.ensure(c.in5, sets_bytes + 16) || !c.ensure(c.in7, rows_bytes + 16) || !c.ensure(c.in8, pieces_bytes + 16))
+    return false;
+  uint8_t *stage = static_cast<uint8_t *>(c.staging(sets_bytes + pieces_bytes + rows_bytes));
+  if (!stage) return fail(GBLS_ERR_HIP);
+  SpanSet *sets = reinterpret_cast<SpanSet *>(stage);
+  SpanPiece *pieces = reinterpret_cast<SpanPiece *>(stage + sets_bytes);
+  uint32_t *rows = reinterpret_cast<uint32_t *>(stage + sets_bytes + pieces_bytes);
+  rows[nw] = 0;
+  auto members = [&](uint32_t slot, const uint32_t **list, uint32_t *len) {
+    const members::View v = slot < g.com_n ? g.mem.get(slot) : members::View();
+    if (v.block == members::kNoBlock) return false;
+    *list = static_cast<const uint32_t *>(d.mem_blocks[v.block].p) + v.off;
+    *len = v.len;
+    return true;
+  };
+  uint32_t w = 0, q = 0;
+  for (size_t i = 0; i < n; i++) {
+    SpanSet &s = sets[i];
+    s.first = q;
+    s.npieces = s.row = s.nbytes = s.M = 0;
+    if (host.com[b + i] == kNoCommittee) {
+      SpanPiece &p = pieces[q++];
+      p.list = nullptr;
+      p.cnt = p.bit = 0;
+      p.slot = kNoCommittee;
+      p.set = (uint32_t)i;
+      if (host.off) {
+        p.list = c.in2.as<uint32_t>() + (host.off[b + i] - base);
+        p.cnt = host.off[b + i + 1] - host.off[b + i];
+      }
+      s.npieces = 1;
+      dev->max_len = std::max(dev->max_len, p.cnt);
+      continue;
+    }
+    s.nbytes = host.bits_off[b + i + 1] - host.bits_off[b + i];
+    s.row = w;
+    bits_repack(&rows[w], host.bits + host.bits_off[b + i], s.nbytes);
+    w += bits_row_words(s.nbytes);
+    s.npieces = span_pieces((uint32_t)i, host.com[b + i], host.cbits[b + i], members, &pieces[q], &s.M);
+    for (uint32_t k = 0; k < s.npieces; k++)
+      dev->max_len = std::max(dev->max_len, span_work(&rows[s.row], s.nbytes, pieces[q + k].bit, pieces[q + k].cnt));
+    q += s.npieces;
+    dev->span_max_pieces = std::max(dev->span_max_pieces, s.npieces);
+  }
+  if (!c.send_staged(c.in5.p, sets, sets_bytes, st) || !c.send_staged(c.in8.p, pieces, pieces_bytes, st) ||
+      !c.send_staged(c.in7.p, rows, rows_bytes, st))
+    return false;
+  dev->idx = c.in2.as<uint32_t>();
+  dev->span_sets = c.in5.p;
+  dev->span_pieces = c.in8.p;
+  dev->span_np = q;
+  dev->bit_rows = c.in7.as<uint32_t>();
+  return true;
+}
+
 // Upload a HOST key source for sets [b, e) as a device key source (d: for aggregation-bit sets).
 bool upload_pks(Ctx &c, const PkSource &host, size_t b, size_t e, hipStream_t st, PkSource *dev,
                 Device *d = nullptr) {
@@ -1412,6 +1491,7 @@ bool upload_pks(Ctx &c, const PkSource &host, size_t b, size_t e, hipStream_t st
   *dev = PkSource();
   if (host.bits_off) {
     if (!host.com || !d) return fail(GBLS_ERR_ARG);
+    if (host.cbits) return upload_span_sets(c, *d, host, b, e, st, dev);
     return upload_bit_sets(c, *d, host, b, e, st, dev);
   }
   if (host.com) {  // committee slots per set, with index ranges (possibly all empty)
@@ -2887,6 +2967,91 @@ int gbls_multi_verify_bits(const uint8_t (*msgs)[32], const uint8_t (*sigs)[96],
   const int cls = (call_flags & GBLS_CALL_BLOCK) ? 1 : 0;
   BlockActive block_active(cls != 0);
   // its own submission, as the committees call (the coalescer's requests carry neither)
+  if (!verify_host(&msgs[0][0], nullptr, &sigs[0][0], sig_status, src, rands, n, off, 1, &v, cls)) {
+    fill(sig_status, n, GBLS_BAD_ENCODING);
+    return GBLS_VERIFY_FAIL;
+  }
+  for (size_t i = 0; i < n; i++)  // MultiVerifier::finish: a decoding error comes first
+    if (sig_status[i] != GBLS_SUCCESS) return sig_status[i];
+  return v;
+}
+
+// ---- span sets (include/grandine_bls_gpu_spans.h): attestations over several committees, a base
+// slot, committee_bits and one bit string per set, cut into (set, committee) pieces (k_spans.hip).
+// the arguments of a span key source (both calls below): a span set has no index range, a plain
+// set neither committee bits nor aggregation bits; the pieces of the call are counted in 32 bits
+static bool spans_args_ok(const uint32_t *com, const uint8_t (*cbits)[8], const uint8_t *bits,
+                          const uint32_t *bits_off, const uint32_t *pk_idx, const uint32_t *pk_off, size_t n) {
+  if (!cbits || !bits_args_ok(com, bits, bits_off, pk_idx, pk_off, n)) return false;
+  uint64_t np = 0;
+  for (size_t i = 0; i < n; i++) {
+    const bool plain = com[i] == GBLS_NO_COMMITTEE;
+    if (plain && !span_mask_empty(cbits[i])) return false;
+    np += plain ? 1 : span_mask_count(cbits[i]);
+  }
+  return np <= 0xffffffffull;
+}
+
+int gbls_g1_aggregate_spans(const uint32_t *com, const uint8_t (*cbits)[8], const uint8_t *bits,
+                            const uint32_t *bits_off, const uint32_t *pk_idx, const uint32_t *pk_off, size_t n,
+                            gbls_p1_affine *out, int32_t *status) {
+  fill(status, n, GBLS_BAD_ENCODING);
+  if (out) std::memset(out, 0, n * sizeof(*out));
+  API_BEGIN
+  if (n == 0) return GBLS_SUCCESS;
+  if (!out || !spans_args_ok(com, cbits, bits, bits_off, pk_idx, pk_off, n)) return fail(GBLS_ERR_ARG), FAILED;
+  PkSource src, dsrc;
+  src.com = com;
+  src.cbits = cbits;
+  src.bits = bits;
+  src.bits_off = bits_off;
+  src.idx = pk_idx;
+  src.off = pk_off;
+  std::shared_lock<std::shared_mutex> rl(g.reg_mu);
+  Device &d = pick_device();
+  Lease L(d);
+  Ctx &c = *L;
+  hipStream_t st = c.own;
+  const g1a *keys = nullptr;
+  const int32_t *pre = nullptr;
+  if (!L.ok() || !c.begin(st) || !upload_pks(c, src, 0, n, st, &dsrc, &d) ||
+      !resolve_pks(c, d, dsrc, n, st, &keys, &pre))
+    return FAILED;
+  if (hipMemcpyAsync(out, keys, n * sizeof(g1a), hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipMemcpyAsync(status, pre, n * 4, hipMemcpyDeviceToHost, st) != hipSuccess)
+    return fail(GBLS_ERR_HIP), FAILED;
+  rl.unlock();  // enqueued: the host wait below does not hold up registry updates
+  if (hipStreamSynchronize(st) != hipSuccess) {
+    fill(status, n, GBLS_BAD_ENCODING);
+    std::memset(out, 0, n * sizeof(*out));
+    return fail(GBLS_ERR_HIP), FAILED;
+  }
+  return GBLS_SUCCESS;
+}
+
+int gbls_multi_verify_spans(const uint8_t (*msgs)[32], const uint8_t (*sigs)[96], const uint32_t *com,
+                            const uint8_t (*cbits)[8], const uint8_t *bits, const uint32_t *bits_off,
+                            const uint32_t *pk_idx, const uint32_t *pk_off, const uint64_t *rands, size_t n,
+                            int32_t *sig_status, uint32_t call_flags) {
+  t_last_error = GBLS_ERR_NONE;
+  if (!sig_status) return fail(GBLS_ERR_ARG), GBLS_VERIFY_FAIL;
+  fill(sig_status, n, GBLS_BAD_ENCODING);
+  API_BEGIN
+  if (n == 0) return GBLS_VERIFY_FAIL;
+  if (!msgs || !sigs || !rands || !spans_args_ok(com, cbits, bits, bits_off, pk_idx, pk_off, n))
+    return fail(GBLS_ERR_ARG), GBLS_VERIFY_FAIL;
+  PkSource src;
+  src.com = com;
+  src.cbits = cbits;
+  src.bits = bits;
+  src.bits_off = bits_off;
+  src.idx = pk_idx;
+  src.off = pk_off;
+  uint32_t off[2] = {0, (uint32_t)n};
+  int32_t v = GBLS_VERIFY_FAIL;
+  const int cls = (call_flags & GBLS_CALL_BLOCK) ? 1 : 0;
+  BlockActive block_active(cls != 0);
+  // its own submission, as the bits call (the coalescer's requests carry neither)
   if (!verify_host(&msgs[0][0], nullptr, &sigs[0][0], sig_status, src, rands, n, off, 1, &v, cls)) {
     fill(sig_status, n, GBLS_BAD_ENCODING);
     return GBLS_VERIFY_FAIL;

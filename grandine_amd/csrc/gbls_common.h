@@ -103,6 +103,15 @@ void launch_g1_committee_keys(hipStream_t st, const g1a *reg, uint32_t nreg, con
 void launch_g1_bits_keys(hipStream_t st, const g1a *reg, uint32_t nreg, const g1a *tab, uint32_t ntab,
                          const void *sets, const uint32_t *rows, uint32_t n, uint32_t max_work, g1a *out,
                          int32_t *status);
+// k_spans.hip -- keys of span sets (committee_bits: several committees per set; gbls_spans.h):
+// pieces = np SpanPiece descriptors, sets = n SpanSet descriptors, rows = the sets' repacked bit
+// strings.  max_work: the longest piece's work (as for launch_g1_bits_keys: the piece kernel's form),
+// max_pieces: the most pieces of one set (the finish's form).  contrib / pflags: np Jacobian points
+// and np words of workspace
+void launch_g1_span_keys(hipStream_t st, const g1a *reg, uint32_t nreg, const g1a *tab, uint32_t ntab,
+                         const void *pieces, const void *sets, const uint32_t *rows, uint32_t np, uint32_t n,
+                         uint32_t max_work, uint32_t max_pieces, void *contrib, uint32_t *pflags, g1a *out,
+                         int32_t *status);
 void launch_sk_to_pk(hipStream_t st, const uint8_t *sks, uint32_t n, g1a *out);
 void launch_sign(hipStream_t st, const uint8_t *sks, const g2a *H, uint32_t n, g2a *out);
 void launch_mad_peak(hipStream_t st, unsigned blocks, uint64_t *sink, uint32_t iters, uint32_t seed);

@@ -129,6 +129,13 @@ struct KeySource {
   const uint32_t *bits_off = nullptr;
   const void *bit_sets = nullptr;
   const uint32_t *bit_rows = nullptr;
+  // span sets (with com, bits and bits_off; gbls_spans.h): com[i] is a base slot and cbits[i] the 8
+  // bytes of committee_bits, one bit string over the named committees.  Device source: the
+  // SpanPiece and SpanSet descriptors (rows in bit_rows), their count and the most pieces of a set.
+  const uint8_t (*cbits)[8] = nullptr;
+  const void *span_pieces = nullptr;
+  const void *span_sets = nullptr;
+  uint32_t span_np = 0, span_max_pieces = 0;
 };
 
 // One caller's batch (host pointers, borrowed for the call).  rands == nullptr: independent

@@ -64,7 +64,8 @@ class Triple:
     ``verify_aggregate``, the message, signature and the KEY LIST whose sum is the key."""
 
     IS_NULL = False
-    __slots__ = ("message", "signature_bytes", "_key", "deferred", "indices", "slot", "committee", "absent", "bits")
+    __slots__ = ("message", "signature_bytes", "_key", "deferred", "indices", "slot", "committee", "absent", "bits",
+                 "span_base", "span_cbits", "span_committees")
 
     def __init__(self, message: bytes = bytes(32), signature_bytes: bytes = None,
                  public_key: "bls.PublicKey" = None):
@@ -77,6 +78,9 @@ class Triple:
         self.committee = None  # ... the committee's member indices
         self.absent = None    # ... and the members whose aggregation bit is clear
         self.bits = None      # ... and the aggregation bits as SSZ bytes
+        self.span_base = None  # verify_aggregate_committees: the base slot, with
+        self.span_cbits = None  # ... committee_bits as its 8 SSZ bytes (bits then spans the named committees)
+        self.span_committees = None  # ... and the named committees' member indices, ascending
 
     def verify_aggregate(self, message, signature_bytes, public_keys, signature_kind=None):
         """verifier.rs:387-405 without the reduce: the keys are kept and summed on the device by
@@ -90,6 +94,7 @@ class Triple:
         # its indices the same way)
         self.indices = None
         self.slot = self.committee = self.absent = self.bits = None
+        self.span_base = self.span_cbits = self.span_committees = None
 
     def verify_aggregate_indexed(self, message, signature_bytes, validator_indices, public_keys,
                                  signature_kind=None):
@@ -129,6 +134,55 @@ class Triple:
         self.committee = committee
         self.absent = [v for v, b in zip(committee, bits) if not b]
         self.bits = raw
+
+    def verify_aggregate_committees(self, message, signature_bytes, base_slot, committee_bits, committees,
+                                    aggregation_bits, public_keys, signature_kind=None):
+        """verify_aggregate_indexed for an attestation over several committees (EIP-7549):
+        ``committee_bits`` (8 SSZ bytes, or an iterable of committee indices below 64) names the
+        committees, which live in table slots ``base_slot + c``; ``committees`` are the named
+        committees' member lists in ascending committee order; ``aggregation_bits`` is the ONE bit
+        string over their concatenation (SSZ ``bytes`` passed through, or bools packed as a
+        Bitvector); ``public_keys`` are the participants' keys.  Keeps the participants' indices,
+        so that every existing path still takes the triple, plus the base slot, the mask and the
+        bits for MultiVerifier.finish's "spans" path."""
+        if isinstance(committee_bits, (bytes, bytearray)):
+            cbits = bytes(committee_bits)
+            if len(cbits) != 8:
+                raise ValueError("committee_bits is a Bitvector[64]: 8 bytes")
+        else:
+            packed = bytearray(8)
+            for c in committee_bits:
+                if not 0 <= int(c) < 64:
+                    raise ValueError("a committee index is below 64")
+                packed[int(c) >> 3] |= 1 << (int(c) & 7)
+            cbits = bytes(packed)
+        committees = [[int(i) for i in c] for c in committees]
+        if len(committees) != sum(bin(b).count("1") for b in cbits):
+            raise ValueError("one member list per named committee")
+        flat = [v for c in committees for v in c]
+        if isinstance(aggregation_bits, (bytes, bytearray)):
+            raw = bytes(aggregation_bits)
+            if len(raw) < (len(flat) + 7) // 8:
+                raise ValueError("one aggregation bit per member of the named committees")
+            bits = [bool(raw[j >> 3] >> (j & 7) & 1) for j in range(len(flat))]
+        else:
+            bits = [bool(b) for b in aggregation_bits]
+            if len(bits) != len(flat):
+                raise ValueError("one aggregation bit per member of the named committees")
+            packed = bytearray((len(bits) + 7) // 8)
+            for j, b in enumerate(bits):
+                packed[j >> 3] |= int(b) << (j & 7)
+            raw = bytes(packed)
+        self.verify_aggregate_indexed(message, signature_bytes, [v for v, b in zip(flat, bits) if b], public_keys,
+                                      signature_kind)
+        self.span_base = int(base_slot)
+        self.span_cbits = cbits
+        self.span_committees = committees
+        self.bits = raw
+
+    def span_slots(self):
+        """The table slots a verify_aggregate_committees triple names, ascending."""
+        return [self.span_base + c for c in range(64) if self.span_cbits[c >> 3] >> (c & 7) & 1]
 
     @property
     def public_key(self) -> "bls.PublicKey":
@@ -228,7 +282,7 @@ class MultiVerifier(Verifier):
     def __init__(self, options: Iterable[VerifierOption] = (), triples: Optional[List[Triple]] = None):
         self.triples: List[Triple] = list(triples or [])
         self.options = set(options)
-        self.last_path = None  # "bits", "committees", "indices" or "points": the key form of the last finish (tests)
+        self.last_path = None  # "spans", "bits", "committees", "indices" or "points": the key form of the last finish (tests)
 
     @classmethod
     def from_triples(cls, triples: List[Triple]) -> "MultiVerifier":  # From<Vec<Triple>>
@@ -258,6 +312,46 @@ class MultiVerifier(Verifier):
                                      signature_kind)
         self.triples.append(t)
 
+    def verify_aggregate_committees(self, message, signature_bytes, base_slot, committee_bits, committees,
+                                    aggregation_bits, public_keys, signature_kind=None):
+        t = Triple()
+        t.verify_aggregate_committees(message, signature_bytes, base_slot, committee_bits, committees,
+                                      aggregation_bits, public_keys, signature_kind)
+        self.triples.append(t)
+
+    def _finish_spans(self, msgs, sigs, randoms, flags):
+        """The "spans" path, or None when the triples do not qualify: at least one triple came
+        through verify_aggregate_committees, every slot it names keeps exactly the members the triple
+        was built from, and the other triples qualify as for "bits" (a single-committee triple is
+        then a span with one bit)."""
+        spans = [t for t in self.triples if t.span_base is not None]
+        if not spans:
+            return None
+        for t in spans:
+            slots = t.span_slots()
+            if not slots or not all(bls.Committees.has_members(s) and bls.Committees.covers(s, c)
+                                    for s, c in zip(slots, t.span_committees)):
+                return None
+        for t in self.triples:
+            if t.span_base is not None:
+                continue
+            if t.slot is not None:
+                if not (bls.Committees.has_members(t.slot) and bls.Committees.covers(t.slot, t.committee)):
+                    return None
+            elif t.indices is None or not bls.Registry.covers(t.indices):
+                return None
+        one = bytes([1]) + bytes(7)
+        base, cbits, fields, lists = [], [], [], []
+        for t in self.triples:
+            if t.span_base is not None:
+                base.append(t.span_base), cbits.append(t.span_cbits), fields.append(t.bits), lists.append(())
+            elif t.slot is not None:
+                base.append(t.slot), cbits.append(one), fields.append(t.bits), lists.append(())
+            else:
+                base.append(None), cbits.append(bytes(8)), fields.append(b""), lists.append(t.indices)
+        self.last_path = "spans"
+        return bls.Signature.multi_verify_compressed_spans(msgs, sigs, base, cbits, fields, lists, randoms, flags)
+
     def finish(self, randoms=None):
         """verifier.rs:301-323."""
         if not self.triples:
@@ -271,7 +365,11 @@ class MultiVerifier(Verifier):
         sigs = [t.signature_bytes for t in self.triples]
         indexed = all(t.indices is not None and bls.Registry.covers(t.indices) for t in self.triples)
         com = [t for t in self.triples if t.slot is not None]
-        if com and all(bls.Committees.has_members(t.slot) and bls.Committees.covers(t.slot, t.committee)
+        # attestations over several committees first: base slot, committee_bits and the one bit string
+        rc = self._finish_spans(msgs, sigs, randoms, flags)
+        if rc is not None:
+            pass  # sent: last_path == "spans"
+        elif com and all(bls.Committees.has_members(t.slot) and bls.Committees.covers(t.slot, t.committee)
                        for t in com) and all(t.indices is not None and bls.Registry.covers(t.indices)
                                              for t in self.triples if t.slot is None):
             # resident members: a committee triple is its slot and its aggregation bits as they

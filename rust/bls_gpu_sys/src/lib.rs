@@ -26,7 +26,9 @@ pub mod ffi;
 pub mod ffi_bits;
 pub mod ffi_committees;
 pub mod ffi_msgcache;
+pub mod ffi_spans;
 pub mod msgcache;
+pub mod spans;
 
 use core::{ffi::c_int, ptr};
 use std::sync::OnceLock;

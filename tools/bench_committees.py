@@ -26,8 +26,20 @@ the aggregation-bit calls (include/grandine_bls_gpu_bits.h), a slot and an SSZ B
 alternating with the two committees forms (the yardstick of that leg; `parent` is left out), and
 each result carries the host bytes a call uploads for its key source (upload_bytes).
 
+With --spans the shape is block8x64x512: a block's 8 attestations over all 64 committees of a slot
+(include/grandine_bls_gpu_spans.h; 512 committees of 512 members, loaded with their members) and 4
+plain single-key sets, the first k members of every committee absent, the forms alternating:
+
+  spans         gbls_multi_verify_spans: base slot, committee_bits and one bit string per set
+  lists         gbls_multi_verify_compressed_ex over the full participant index lists
+  three         the same result without the spans call, as three submissions: gbls_g1_aggregate_bits
+                over the 512 (set, committee) pieces, the host regroup, and
+                gbls_multi_verify_compressed_ex over the points, 64 keys per set
+  keys_spans    gbls_g1_aggregate_spans (the keys alone)
+
   python tools/bench_committees.py                       # both shapes, one JSON line per point
   python tools/bench_committees.py --bits                # ... the aggregation-bit leg
+  python tools/bench_committees.py --spans               # the span-set leg (its own shape)
   GBLS_COMMITTEE_ROW_MIN=1 python tools/bench_committees.py --tuning --keys-only
 """
 import argparse
@@ -66,6 +78,118 @@ def summary(f):
     return {"median_us": round(statistics.median(f), 1), "min_us": round(min(f), 1), "max_us": round(max(f), 1)}
 
 
+def spans_leg(a, G, F, L, emit, absent_counts):
+    """block8x64x512: the spans call against the two forms available without it."""
+    nset, per_set, size, nplain = 8, 64, 512, 4
+    ncom, n = nset * per_set, nset + nplain
+    nreg = ncom * size
+    seed = b"bench-committees/block8x64x512"
+    sks, comp = F.registry(nreg, seed)
+    if F.load_registry(comp).any():
+        raise SystemExit("registry load failed")
+    perm, off = F.committees(nreg, ncom, 7)
+    perm_c = np.ascontiguousarray(perm, dtype=np.uint32)
+    off_c = np.ascontiguousarray(off, dtype=np.uint32)
+    st = G.i32_array(ncom)
+    ptr = lambda x: x.ctypes.data_as(ctypes.c_void_p)
+    rc = L.gbls_committees_set_members(0, ptr(perm_c), ptr(off_c), ncom, st)
+    if rc != G.SUCCESS or any(st[c] for c in range(ncom)):
+        raise SystemExit("gbls_committees_set_members rc=%d" % rc)
+    emit({"shape": "block8x64x512", "sets": n, "span_sets": nset, "committees_per_set": per_set, "size": size,
+          "plain_sets": nplain, "registry": nreg})
+    sk = np.array(sks, dtype=object)
+    totals = [int(sum(sk[perm[off[c]:off[c + 1]]])) for c in range(ncom)]
+    plain = [int(perm[off[7 * i + 3]]) for i in range(nplain)]
+    msgs = F.messages(n, seed)
+    rands = (ctypes.c_uint64 * n)(*F.rands(n, n + size))
+    sig_st = G.i32_array(max(n, ncom + nplain))
+    full = np.uint8(0xFF)
+    for k in absent_counts:
+        sums = []
+        for i in range(nset):
+            t = 0
+            for c in range(per_set * i, per_set * (i + 1)):
+                t += totals[c] - int(sum(sk[perm[off[c]:off[c] + k]]))
+            sums.append(t % F.R_ORDER)
+        sums += [sks[v] for v in plain]
+        sigs = F.sign(sums, msgs)
+        sig_c = ctypes.create_string_buffer(96 * n)
+        G.check(L.gbls_g2_compress(sigs, n, sig_c), "gbls_g2_compress")
+        # spans: per set the base slot, all 64 committee bits and one Bitlist over the 64 committees
+        base = np.array([per_set * i for i in range(nset)] + [G.NO_COMMITTEE] * nplain, dtype=np.uint32)
+        masks = np.zeros((n, 8), dtype=np.uint8)
+        masks[:nset] = full
+        fields = []
+        for i in range(nset):
+            bits = np.zeros(8 * (per_set * size // 8 + 1), dtype=np.uint8)
+            for c in range(per_set):
+                bits[c * size + k:(c + 1) * size] = 1
+            bits[per_set * size] = 1  # the delimiter
+            fields.append(np.packbits(bits, bitorder="little").tobytes())
+        s_all = ctypes.create_string_buffer(b"".join(fields), sum(len(x) for x in fields))
+        s_off = np.zeros(n + 1, dtype=np.uint32)
+        s_off[1:nset + 1] = np.cumsum([len(x) for x in fields])
+        s_off[nset + 1:] = s_off[nset]
+        q_idx = np.array(plain, dtype=np.uint32)
+        q_off = np.zeros(n + 1, dtype=np.uint32)
+        q_off[nset + 1:] = np.arange(1, nplain + 1)
+        # lists: every participant's index
+        lists = [np.concatenate([perm[off[c] + k:off[c + 1]] for c in range(per_set * i, per_set * (i + 1))])
+                 for i in range(nset)] + [np.array([v]) for v in plain]
+        l_idx = np.ascontiguousarray(np.concatenate(lists), dtype=np.uint32)
+        l_off = np.zeros(n + 1, dtype=np.uint32)
+        l_off[1:] = np.cumsum([len(v) for v in lists])
+        # three: one single-committee Bitlist per (set, committee) piece, then the plain sets
+        npc = ncom + nplain
+        p_slots = np.array(list(range(ncom)) + [G.NO_COMMITTEE] * nplain, dtype=np.uint32)
+        one = np.zeros(8 * (size // 8 + 1), dtype=np.uint8)
+        one[k:size] = 1
+        one[size] = 1
+        piece = np.packbits(one, bitorder="little").tobytes()
+        p_all = ctypes.create_string_buffer(piece * ncom, len(piece) * ncom)
+        p_off = np.zeros(npc + 1, dtype=np.uint32)
+        p_off[1:ncom + 1] = len(piece) * np.arange(1, ncom + 1)
+        p_off[ncom + 1:] = p_off[ncom]
+        pq_off = np.zeros(npc + 1, dtype=np.uint32)
+        pq_off[ncom + 1:] = np.arange(1, nplain + 1)
+        points = ctypes.create_string_buffer(96 * npc)
+        g_off = np.zeros(n + 1, dtype=np.uint32)
+        keys_out = ctypes.create_string_buffer(96 * n)
+        upload = {"spans": 4 * n + 8 * n + 4 * (n + 1) + int(s_off[n]) + 4 * nplain + 4 * (n + 1),
+                  "lists": 4 * (n + 1) + 4 * int(l_off[n]),
+                  "three": 4 * npc + 4 * (npc + 1) + int(p_off[npc]) + 4 * nplain + 4 * (npc + 1) + 96 * npc + 4 * (n + 1)}
+
+        def call(which):
+            t0 = time.perf_counter()
+            if which == "spans":
+                rc = L.gbls_multi_verify_spans(msgs, sig_c, ptr(base), ptr(masks), s_all, ptr(s_off), ptr(q_idx),
+                                               ptr(q_off), rands, n, sig_st, 0)
+            elif which == "lists":
+                rc = L.gbls_multi_verify_compressed_ex(msgs, sig_c, None, ptr(l_idx), ptr(l_off), rands, n, sig_st, 0)
+            elif which == "three":
+                rc = L.gbls_g1_aggregate_bits(ptr(p_slots), p_all, ptr(p_off), ptr(q_idx), ptr(pq_off), npc, points,
+                                              sig_st)
+                if rc == G.SUCCESS:  # the regroup: the pieces are in set order, so it is the offsets
+                    g_off[1:nset + 1] = per_set * np.arange(1, nset + 1)
+                    g_off[nset + 1:] = ncom + np.arange(1, nplain + 1)
+                    rc = L.gbls_multi_verify_compressed_ex(msgs, sig_c, points, None, ptr(g_off), rands, n, sig_st, 0)
+            else:
+                rc = L.gbls_g1_aggregate_spans(ptr(base), ptr(masks), s_all, ptr(s_off), ptr(q_idx), ptr(q_off), n,
+                                               keys_out, sig_st)
+            dt = time.perf_counter() - t0
+            if rc != G.SUCCESS:
+                raise SystemExit("block8x64x512 absent=%d %s: rc=%d err=%d" % (k, which, rc, L.gbls_last_error()))
+            return dt
+
+        kinds = (["keys_spans"] if a.keys_only else ["spans", "lists", "three", "keys_spans"])
+        f, calls = timed(call, kinds, a.warmup, a.window, a.runs)
+        res = {"shape": "block8x64x512", "sets": n, "absent": k, "calls_per_run": calls, "upload_bytes": upload}
+        for kind in kinds:
+            res[kind] = summary(f[kind])
+            res[kind]["runs_us"] = [round(x, 1) for x in f[kind]]
+        emit(res)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--runs", type=int, default=5)
@@ -77,6 +201,8 @@ def main():
     ap.add_argument("--keys-only", action="store_true", help="only the key resolution")
     ap.add_argument("--bits", action="store_true",
                     help="the aggregation-bit calls beside the two committees forms, full calls and keys alone")
+    ap.add_argument("--spans", action="store_true",
+                    help="the span-set leg: block8x64x512 through the spans call and the two forms without it")
     ap.add_argument("--out", default="", help="also append the JSON lines to this file")
     ap.add_argument("--tuning", action="store_true", help="let the engine read its GBLS_* tuning variables")
     a = ap.parse_args()
@@ -95,8 +221,10 @@ def main():
         lines.append(res)
         print(json.dumps(res), flush=True)
 
+    if a.spans:
+        spans_leg(a, G, F, L, emit, [int(x) for x in a.absent.split(",")] if a.absent else [0, 5, 51, 256])
     for name, ncom, size in SHAPES:
-        if want and name not in want:
+        if a.spans or (want and name not in want):
             continue
         nreg = ncom * size
         seed = b"bench-committees/" + name.encode()
