@@ -8,7 +8,8 @@
 // 12 slots of 16 words (coefficient c at words [16 c, 16 c + 16), lane j's limb at word j).
 //
 // Value contract: products < 1.0001 p; R1 values < 14.001 p; Fp12 coefficients (R2
-// outputs, conj, Frobenius) < 128 p; a presum of <= 8 coefficients < 1024 p < 2^392, the
+// outputs, Frobenius) < 128 p and conj outputs <= 128 p (128 p exactly for a zero limb
+// image: the bias minus nothing); a presum of <= 8 coefficients <= 1024 p < 2^392, the
 // product's input bound.  Every stored limb is < 2^28 + 2^9.
 #pragma once
 #include "bls_dfp.h"
@@ -310,8 +311,9 @@ __device__ __forceinline__ void exp_x_cyc(Eng &e, uint32_t *c, const uint32_t *a
 // (-2p, p) range argument) tolerate.  The exit test normalizes g fully, only when its low 30
 // bits are 0 (at the end, or with probability 2^-30).  26-28 batches for a random input
 // (tools/inv_wave_model.py: the same limb arithmetic in Python, checked on 3000 inputs);
-// x, out: 12 canonical words in LDS (x = 0 gives garbage, never a hang).  All 64 lanes of
-// one wave call it.
+// x, out: 12 canonical words in LDS, out = x^-1 mod p as plain integers (x = 0 gives garbage,
+// never a hang).  All 64 lanes of one wave call it; it returns the number of batches run (for
+// tools/ubench/w12d_check).
 __device__ __forceinline__ int32_t inv_lane_shift_dn(int64_t t, int32_t &carry_out) {
   // new limb j = (t_(j+1) & M30) + (t_j >> 30), then one carry pass; top limb signed
   const uint32_t j = threadIdx.x & 63u;
@@ -333,7 +335,7 @@ __device__ __forceinline__ int32_t inv_normalize_full(int32_t x) {  // 12 carry 
   }
   return x;
 }
-__device__ __forceinline__ void inv_wave(uint32_t *out, const uint32_t *x) {
+__device__ __forceinline__ int inv_wave(uint32_t *out, const uint32_t *x) {
   using namespace binv;
   const uint32_t j = threadIdx.x & 63u;
   S30 Pc;
@@ -350,7 +352,9 @@ __device__ __forceinline__ void inv_wave(uint32_t *out, const uint32_t *x) {
     g = (int32_t)((pair >> sh) & (uint64_t)M30);
   }
   int32_t eta = -1;
+  int batches = 0;
   for (int guard = 0; guard < 40; guard++) {
+    batches = guard + 1;
     const uint32_t f0 = (uint32_t)__builtin_amdgcn_readlane(f, 0);
     const uint32_t g0 = (uint32_t)__builtin_amdgcn_readlane(g, 0);
     Mat t;
@@ -393,6 +397,7 @@ __device__ __forceinline__ void inv_wave(uint32_t *out, const uint32_t *x) {
     }
     out[j] = (uint32_t)acc;
   }
+  return batches;
 }
 
 // ---- the easy part of the final exponentiation, f -> f^((p^6 - 1)(p^2 + 1)), with one Fp
