@@ -484,7 +484,8 @@ __device__ __forceinline__ void gang_line_dbl(g2h &T, fp2 &L0, fp2 &L2, fp2 &L3,
 //   level 1: y2 Z1, x2 Z1                       -> theta, lambda
 //   level 2: theta x2, lambda y2, theta^2, lambda^2
 //   level 3: lambda^3, lambda^2 X1, theta^2 Z1   -> A
-//   level 4: lambda A, theta (R - A), lambda^3 Y1, lambda^3 Z1
+//   level 4: lambda A, theta (R - A), v^3 Y1, v^3 Z1   (v^3 = -lambda^3; X3 and the second
+//            product are negated afterwards: X3 = v A, u (R - A) with u = -theta, v = -lambda)
 __device__ __forceinline__ void gang_line_add_aff(g2h &T, const g2a &Q, fp2 &L0, fp2 &L2, fp2 &L3,
                                                   int q) {
   fp2 a, b, s, yZ, xZ, th, la;
