@@ -122,6 +122,11 @@ EXPORTS_SPANS = [
     "gbls_g1_aggregate_spans",
     "gbls_multi_verify_spans",
 ]
+# include/grandine_bls_gpu_each.h (span sets: per-set and per-item verdicts, merged across callers)
+EXPORTS_EACH = [
+    "gbls_verify_each_spans",
+    "gbls_verify_items_spans",
+]
 # include/grandine_bls_gpu_msgcache.h (message line cache)
 EXPORTS_MSGCACHE = [
     "gbls_msgcache_configure",
@@ -230,16 +235,20 @@ def load_library():
                 "gbls_g1_aggregate_spans": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
                 "gbls_multi_verify_spans": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp,
                                                        _c.c_uint32]),
+                "gbls_verify_each_spans": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+                "gbls_verify_items_spans": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz,
+                                                       _vp, _vp, _vp, _c.c_uint32]),
                 "gbls_msgcache_configure": (_c.c_int, [_sz]),
                 "gbls_msgcache_slots": (_sz, []),
                 "gbls_msgcache_clear": (_c.c_int, []),
                 "gbls_msgcache_stats": (_c.c_int, [_vp]),
             }
             for name, (res, args) in sig.items():
-                # an experiment build (GBLS_LIB) may predate the message line cache, the bits or the
-                # spans calls: A/B tools load it and leave those entries alone; the package's own
-                # library must have them
-                if _override and name in EXPORTS_MSGCACHE + EXPORTS_BITS + EXPORTS_SPANS and not hasattr(lib, name):
+                # an experiment build (GBLS_LIB) may predate the message line cache, the bits, the
+                # spans or the each calls: A/B tools load it and leave those entries alone; the
+                # package's own library must have them
+                if (_override and name in EXPORTS_MSGCACHE + EXPORTS_BITS + EXPORTS_SPANS + EXPORTS_EACH
+                        and not hasattr(lib, name)):
                     continue
                 fn = getattr(lib, name)
                 fn.restype = res

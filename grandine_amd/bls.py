@@ -416,6 +416,73 @@ class Signature:
             G.u64_array(randoms), n, st, call_flags)
 
     @staticmethod
+    def _span_sets(messages, signature_bytes, base_slots, committee_bits, bitfields, validator_indices):
+        """The sets of multi_verify_compressed_spans as the C arguments (msgs, sigs, com, cbits, bits,
+        bits_off, pk_idx, pk_off) and their number."""
+        msgs = [bytes(m) for m in messages]
+        sigs = [bytes(s) for s in signature_bytes]
+        com = [G.NO_COMMITTEE if c is None else int(c) for c in base_slots]
+        masks = [bytes(b or bytes(8)) for b in committee_bits]
+        fields = [bytes(b or b"") for b in bitfields]
+        idx = [list(v or ()) for v in validator_indices]
+        n = len(sigs)
+        if len(msgs) != n or len(idx) != n or len(com) != n or len(fields) != n or len(masks) != n:
+            raise ValueError("one message, base slot, committee_bits, bit string and index list per signature")
+        if any(len(m) != 32 for m in msgs) or any(len(s) != 96 for s in sigs) or any(len(b) != 8 for b in masks):
+            raise ValueError("messages must be 32-byte signing roots, signatures 96 bytes, committee_bits 8 bytes")
+        off, boff = [0], [0]
+        for v, b in zip(idx, fields):
+            off.append(off[-1] + len(v))
+            boff.append(boff[-1] + len(b))
+        flat = [i for v in idx for i in v]
+        return (G.buf(b"".join(msgs)), G.buf(b"".join(sigs)), G.u32_array(com), G.buf(b"".join(masks)),
+                G.buf(b"".join(fields)), G.u32_array(boff), G.u32_array(flat or [0]), G.u32_array(off)), n
+
+    @staticmethod
+    def verify_each_spans(messages: Iterable[bytes], signature_bytes: Iterable[bytes], base_slots: Iterable[int],
+                          committee_bits: Iterable[bytes], bitfields: Iterable[bytes],
+                          validator_indices: Iterable[Sequence[int]]) -> List:
+        """verify_batch_compressed over the sets of multi_verify_compressed_spans
+        (gbls_verify_each_spans): every set its own check, ONE coalesced submission.  Per set:
+        (signature status, key status, ok) -- the decompression status, the status of the set's key
+        (nonzero: a malformed attestation, not an invalid signature) and whether it verifies."""
+        args, n = Signature._span_sets(messages, signature_bytes, base_slots, committee_bits, bitfields,
+                                       validator_indices)
+        if n == 0:
+            return []
+        L = G.lib()
+        st, kst, v = G.i32_array(n), G.i32_array(n), G.i32_array(n)
+        G.check(L.gbls_verify_each_spans(*args, n, st, kst, v), "gbls_verify_each_spans")
+        return [(st[i], kst[i], v[i] == G.SUCCESS) for i in range(n)]
+
+    @staticmethod
+    def verify_items_spans(messages: Iterable[bytes], signature_bytes: Iterable[bytes], base_slots: Iterable[int],
+                           committee_bits: Iterable[bytes], bitfields: Iterable[bytes],
+                           validator_indices: Iterable[Sequence[int]], item_offsets: Sequence[int],
+                           randoms: Sequence[int] = None, call_flags: int = 0, with_statuses: bool = False):
+        """Several independent multi_verify batches over such sets in ONE coalesced submission
+        (gbls_verify_items_spans): sets item_offsets[s] .. item_offsets[s + 1] form item s.  Returns
+        one bool per item; with_statuses: (those, per set (signature status, key status))."""
+        args, n = Signature._span_sets(messages, signature_bytes, base_slots, committee_bits, bitfields,
+                                       validator_indices)
+        seg = [int(o) for o in item_offsets]
+        nseg = len(seg) - 1
+        if nseg < 0 or seg[0] != 0 or seg[-1] != n or any(a > b for a, b in zip(seg, seg[1:])):
+            raise ValueError("item offsets run from 0 to the number of sets, nondecreasing")
+        if n == 0 or nseg == 0:
+            return ([False] * nseg, []) if with_statuses else [False] * nseg
+        if randoms is None:
+            randoms = [secrets.randbits(64) or 1 for _ in range(n)]
+        if len(randoms) != n:
+            raise ValueError("one scalar per set")
+        L = G.lib()
+        st, kst, v = G.i32_array(n), G.i32_array(n), G.i32_array(nseg)
+        G.check(L.gbls_verify_items_spans(*args, G.u64_array(randoms), n, G.u32_array(seg), nseg, st, kst, v,
+                                          call_flags), "gbls_verify_items_spans")
+        verdicts = [v[s] == G.SUCCESS for s in range(nseg)]
+        return (verdicts, [(st[i], kst[i]) for i in range(n)]) if with_statuses else verdicts
+
+    @staticmethod
     def verify_batch_compressed(messages: Iterable[bytes], signature_bytes: Iterable[bytes],
                                 public_keys: Iterable) -> List:
         """SingleVerifier::extend's try_from + verify per triple (verifier.rs:215-236) as ONE

@@ -37,6 +37,7 @@
 #include "../../include/grandine_bls_gpu_committees.h"
 #include "../../include/grandine_bls_gpu_msgcache.h"
 #include "../../include/grandine_bls_gpu_bits.h"
+#include "../../include/grandine_bls_gpu_each.h"
 #include "../../include/grandine_bls_gpu_spans.h"
 #include "gbls_common.h"
 #include "gbls_bits.h"
@@ -1587,14 +1588,16 @@ void mc_finish(Ctx &c, const int32_t *seg_verdicts, bool all_ok) {
 // verdicts (host) when `verdicts`, or else the Miller partial + error flag of the single
 // segment, copied device-to-device (hipMemcpyPeerAsync, xGMI) to part_dst / err_dst on
 // device dst_dev.  rands == nullptr: independent single checks (r_i = 1, signature subgroup
-// check, one segment per set).  Enqueues only; the caller synchronises `c.own` (or waits on it).
+// check, one segment per set).  key_status (a span source only): the sets' key statuses, copied
+// to key_status + b.  Enqueues only; the caller synchronises `c.own` (or waits on it).
 bool enqueue_host_batch(Ctx &c, Device &d, const uint8_t *msgs, const g2a *sigs,
                         const uint8_t *sigs_c, int32_t *sig_status, const PkSource &src,
                         const uint64_t *rands, size_t b, size_t e, const uint32_t *seg,
                         size_t nseg, int32_t *verdicts, fp12 *part_dst, int32_t *err_dst,
-                        int dst_dev) {
+                        int dst_dev, int32_t *key_status = nullptr) {
   hipStream_t st = c.own;
   size_t n = e - b;
+  if (key_status && !src.cbits) return fail(GBLS_ERR_ARG);  // the statuses of a span source only
   if (!c.begin(st)) return false;
   const bool single = rands == nullptr;
   // GBLS_INIT_DEDUP: this shard's sets grouped by message (per segment).  Without duplicates, or
@@ -1669,15 +1672,19 @@ bool enqueue_host_batch(Ctx &c, Device &d, const uint8_t *msgs, const g2a *sigs,
     HIPCHK(hipMemcpyPeerAsync(err_dst, dst_dev, c.err.p, d.hipdev, 4, st));
   }
   if (sigs_c) HIPCHK(hipMemcpyAsync(sig_status + b, c.sigst.p, n * 4, hipMemcpyDeviceToHost, st));
+  // a span source's keys are always resolved (resolve_pks, side stream 1, joined before the Miller
+  // product): this shard's slice of their statuses
+  if (key_status && n) HIPCHK(hipMemcpyAsync(key_status + b, c.pre.p, n * 4, hipMemcpyDeviceToHost, st));
   return true;
 }
 
 // Host-pointer batch verification over every engine device.  Signatures are points
 // (sigs) or, for MultiVerifier::finish, compressed bytes (sigs_c, 96 B each) decompressed on
-// the device with their statuses written to sig_status.
+// the device with their statuses written to sig_status.  key_status (optional, a span source
+// only): every set's key status, each shard writing its slice.
 bool verify_host(const uint8_t *msgs, const g2a *sigs, const uint8_t *sigs_c, int32_t *sig_status,
                  const PkSource &src, const uint64_t *rands, size_t n, const uint32_t *seg_off,
-                 size_t nseg, int32_t *verdicts, int cls = 0) {
+                 size_t nseg, int32_t *verdicts, int cls = 0, int32_t *key_status = nullptr) {
   std::shared_lock<std::shared_mutex> rl(g.reg_mu);
   const size_t ndev = g.devs.size();
   // ---- one large batch: per-device Miller partials, gathered device-to-device onto device 0
@@ -1706,7 +1713,7 @@ bool verify_host(const uint8_t *msgs, const g2a *sigs, const uint8_t *sigs_c, in
       uint32_t seg[2] = {0, (uint32_t)(e - b)};
       ok = L.ok() && enqueue_host_batch(*L, d, msgs, sigs, sigs_c, sig_status, src, rands, b, e,
                                         seg, 1, nullptr, L0->part.as<fp12>() + j,
-                                        L0->err.as<int32_t>() + j, d0.hipdev);
+                                        L0->err.as<int32_t>() + j, d0.hipdev, key_status);
       if (!ok) break;
       hipEvent_t ev;
       if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
@@ -1757,7 +1764,8 @@ bool verify_host(const uint8_t *msgs, const g2a *sigs, const uint8_t *sigs_c, in
     leases.emplace_back(new Lease(d, cls));
     Lease &L = *leases.back();
     ok = L.ok() && enqueue_host_batch(*L, d, msgs, sigs, sigs_c, sig_status, src, rands, b, e,
-                                      segs[j].data(), s1 - s0, verdicts + s0, nullptr, nullptr, 0);
+                                      segs[j].data(), s1 - s0, verdicts + s0, nullptr, nullptr, 0,
+                                      key_status);
   }
   rl.unlock();  // enqueued: the host waits do not hold up registry updates
   for (auto &L : leases)
@@ -1792,7 +1800,7 @@ bool coalesced_verify(CoReq &r) {
   if (g.block_hold) cfg.hold = &g.block_active;
   bool ok = co.submit(r, cfg, [](CoReq &m) {
     m.ok = verify_host(m.msgs, m.sigs, m.sigs_c, m.sig_status, m.src, m.rands, m.n, m.seg_off,
-                       m.nseg, m.verdicts, m.prio);
+                       m.nseg, m.verdicts, m.prio, m.key_status);
     m.err = t_last_error;  // the leader's thread-local code, handed to every merged caller
   });
   t_last_error = r.err;
@@ -3059,6 +3067,70 @@ int gbls_multi_verify_spans(const uint8_t (*msgs)[32], const uint8_t (*sigs)[96]
   for (size_t i = 0; i < n; i++)  // MultiVerifier::finish: a decoding error comes first
     if (sig_status[i] != GBLS_SUCCESS) return sig_status[i];
   return v;
+}
+
+// ---- per-set and per-item verdicts over span sets (include/grandine_bls_gpu_each.h).  Both calls
+// are one coalescer request over a host span source: nseg segments of a random-linear-combination
+// batch (rands), or n independent single checks (rands == nullptr, identity segments), with the
+// signatures' and the keys' statuses read back beside the verdicts.
+static int spans_checks_co(const uint8_t (*msgs)[32], const uint8_t (*sigs)[96], const uint32_t *com,
+                           const uint8_t (*cbits)[8], const uint8_t *bits, const uint32_t *bits_off,
+                           const uint32_t *pk_idx, const uint32_t *pk_off, const uint64_t *rands, size_t n,
+                           const uint32_t *seg_off, size_t nseg, int32_t *sig_status, int32_t *key_status,
+                           int32_t *verdicts, uint32_t call_flags, bool each) {
+  auto prefill = [&] {
+    if (verdicts) fill(verdicts, nseg, GBLS_VERIFY_FAIL);
+    if (sig_status) fill(sig_status, n, GBLS_BAD_ENCODING);
+    if (key_status) fill(key_status, n, GBLS_BAD_ENCODING);
+  };
+  prefill();
+  API_BEGIN
+  if (n == 0 || nseg == 0) return GBLS_SUCCESS;
+  if (!msgs || !sigs || !sig_status || !key_status || !verdicts ||
+      !spans_args_ok(com, cbits, bits, bits_off, pk_idx, pk_off, n))
+    return fail(GBLS_ERR_ARG), FAILED;
+  std::vector<uint32_t> ident;
+  if (each) {  // independent checks: one segment per set
+    ident.resize(n + 1);
+    for (size_t i = 0; i <= n; i++) ident[i] = (uint32_t)i;
+    seg_off = ident.data();
+  } else if (!rands || !valid_offsets(seg_off, nseg, n)) {
+    return fail(GBLS_ERR_ARG), FAILED;
+  }
+  CoReq r{&msgs[0][0], nullptr, PkSource(), rands, n, seg_off, nseg, verdicts};
+  r.src.com = com;
+  r.src.cbits = cbits;
+  r.src.bits = bits;
+  r.src.bits_off = bits_off;
+  r.src.idx = pk_idx;
+  r.src.off = pk_off;
+  r.sigs_c = &sigs[0][0];
+  r.sig_status = sig_status;
+  r.key_status = key_status;
+  r.prio = (call_flags & GBLS_CALL_BLOCK) ? 1 : 0;
+  BlockActive block_active(r.prio != 0);
+  if (!coalesced_verify(r)) {
+    prefill();
+    return FAILED;
+  }
+  return GBLS_SUCCESS;
+}
+
+int gbls_verify_each_spans(const uint8_t (*msgs)[32], const uint8_t (*sigs)[96], const uint32_t *com,
+                           const uint8_t (*cbits)[8], const uint8_t *bits, const uint32_t *bits_off,
+                           const uint32_t *pk_idx, const uint32_t *pk_off, size_t n, int32_t *sig_status,
+                           int32_t *key_status, int32_t *verdicts) {
+  return spans_checks_co(msgs, sigs, com, cbits, bits, bits_off, pk_idx, pk_off, nullptr, n, nullptr, n,
+                         sig_status, key_status, verdicts, 0, true);
+}
+
+int gbls_verify_items_spans(const uint8_t (*msgs)[32], const uint8_t (*sigs)[96], const uint32_t *com,
+                            const uint8_t (*cbits)[8], const uint8_t *bits, const uint32_t *bits_off,
+                            const uint32_t *pk_idx, const uint32_t *pk_off, const uint64_t *rands, size_t n,
+                            const uint32_t *seg_off, size_t nseg, int32_t *sig_status, int32_t *key_status,
+                            int32_t *verdicts, uint32_t call_flags) {
+  return spans_checks_co(msgs, sigs, com, cbits, bits, bits_off, pk_idx, pk_off, rands, n, seg_off, nseg,
+                         sig_status, key_status, verdicts, call_flags, false);
 }
 
 // ---- message line cache (include/grandine_bls_gpu_msgcache.h).  None of these needs a device:

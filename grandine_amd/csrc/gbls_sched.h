@@ -155,13 +155,18 @@ struct Request {
   int32_t *verdicts;
   const uint8_t *sigs_c = nullptr;  // compressed signatures instead of sigs (96 B each)
   int32_t *sig_status = nullptr;    // their decompression statuses (with sigs_c)
+  int32_t *key_status = nullptr;    // the sets' key statuses (a span source only)
   int prio = 0;                     // 1: block import
   bool done = false, ok = false;
   int err = 0;                      // the verifier's side-channel error code
+  bool spans() const { return src.cbits != nullptr; }
+  // A span source (com, cbits, bits, bits_off; idx and off for its plain sets, off == nullptr
+  // when it has none) is a kind of its own whether or not it carries index ranges.
   int kind() const {
-    return (src.pts ? 1 : 0) | (src.off ? 2 : 0) | (sigs_c ? 4 : 0) | (rands ? 0 : 8);
+    const int sig = (sigs_c ? 4 : 0) | (rands ? 0 : 8);
+    return spans() ? 16 | sig : (src.pts ? 1 : 0) | (src.off ? 2 : 0) | sig;
   }
-  size_t nkeys() const { return src.off ? src.off[n] : n; }
+  size_t nkeys() const { return src.off ? src.off[n] : spans() ? 0 : n; }
 };
 
 struct Config {
@@ -181,7 +186,9 @@ struct Config {
 
 // Runs the requests of `batch` (all of one kind) as ONE segmented verification: the merged
 // request is handed to verify(Req &) (which sets ok and err), then every caller's verdicts and
-// signature statuses are copied back from its own range.
+// signature statuses (and, for span sources, key statuses) are copied back from its own range.
+// Span sources: com and cbits are concatenated, the bit strings too with bits_off rebased, the
+// plain sets' indices with off rebased (a request without off contributes empty ranges).
 template <class Req, class Verify>
 void run_merged(std::vector<Req *> &batch, Verify &&verify) {
   if (batch.size() == 1) {
@@ -197,7 +204,7 @@ void run_merged(std::vector<Req *> &batch, Verify &&verify) {
     nk += r->nkeys();
   }
   const Req &r0 = *batch[0];
-  const bool comp = r0.sigs_c != nullptr, single = r0.rands == nullptr;
+  const bool comp = r0.sigs_c != nullptr, single = r0.rands == nullptr, spans = r0.spans();
   std::vector<uint8_t> msgs(32 * n), sigc(comp ? 96 * n : 0);
   std::vector<G2> sigs(comp ? 0 : n);
   std::vector<int32_t> sst(comp ? n : 0, 1 /* BAD_ENCODING until decoded */);
@@ -208,9 +215,20 @@ void run_merged(std::vector<Req *> &batch, Verify &&verify) {
     pts.resize(nk);
   else
     idx.resize(nk);
-  if (r0.src.off) off.resize(n + 1);
+  if (r0.src.off || spans) off.resize(n + 1);
+  std::vector<uint32_t> com, boff;
+  std::vector<uint8_t> cbits, bits;
+  std::vector<int32_t> kst(spans ? n : 0, 1 /* BAD_ENCODING until resolved */);
+  if (spans) {
+    size_t nb = 0;
+    for (Req *r : batch) nb += r->src.bits_off[r->n];
+    com.resize(n);
+    cbits.resize(8 * n);
+    bits.resize(nb);
+    boff.resize(n + 1);
+  }
   std::vector<int32_t> v(nseg, 5 /* VERIFY_FAIL */);
-  size_t at = 0, sat = 0, kat = 0;
+  size_t at = 0, sat = 0, kat = 0, bat = 0;
   seg[0] = 0;
   for (Req *r : batch) {
     std::memcpy(&msgs[32 * at], r->msgs, 32 * r->n);
@@ -222,10 +240,20 @@ void run_merged(std::vector<Req *> &batch, Verify &&verify) {
     const size_t k = r->nkeys();
     if (r0.src.pts)
       std::memcpy(&pts[kat], r->src.pts, k * sizeof(G1));
-    else
+    else if (k)
       std::memcpy(&idx[kat], r->src.idx, k * 4);
-    if (r0.src.off)
-      for (size_t i = 0; i <= r->n; i++) off[at + i] = (uint32_t)(kat + r->src.off[i]);
+    if (r0.src.off || spans)
+      for (size_t i = 0; i <= r->n; i++) off[at + i] = (uint32_t)(kat + (r->src.off ? r->src.off[i] : 0));
+    if (spans) {
+      const size_t nb = r->src.bits_off[r->n];
+      if (r->n) {
+        std::memcpy(&com[at], r->src.com, r->n * 4);
+        std::memcpy(&cbits[8 * at], r->src.cbits, 8 * r->n);
+      }
+      if (nb) std::memcpy(&bits[bat], r->src.bits, nb);
+      for (size_t i = 0; i <= r->n; i++) boff[at + i] = (uint32_t)(bat + r->src.bits_off[i]);
+      bat += nb;
+    }
     for (size_t s = 1; s <= r->nseg; s++) seg[sat + s] = (uint32_t)(at + r->seg_off[s]);
     at += r->n;
     sat += r->nseg;
@@ -237,7 +265,14 @@ void run_merged(std::vector<Req *> &batch, Verify &&verify) {
     m.src.pts = pts.data();
   else
     m.src.idx = idx.data();
-  if (r0.src.off) m.src.off = off.data();
+  if (r0.src.off || spans) m.src.off = off.data();
+  if (spans) {
+    m.src.com = com.data();
+    m.src.cbits = reinterpret_cast<const uint8_t(*)[8]>(cbits.data());
+    m.src.bits = bits.data();
+    m.src.bits_off = boff.data();
+    m.key_status = kst.data();
+  }
   if (comp) {
     m.sigs_c = sigc.data();
     m.sig_status = sst.data();
@@ -249,6 +284,7 @@ void run_merged(std::vector<Req *> &batch, Verify &&verify) {
   for (Req *r : batch) {
     std::memcpy(r->verdicts, &v[sat], r->nseg * 4);
     if (comp) std::memcpy(r->sig_status, &sst[at], r->n * 4);
+    if (spans && r->key_status) std::memcpy(r->key_status, &kst[at], r->n * 4);
     sat += r->nseg;
     at += r->n;
     r->ok = m.ok;

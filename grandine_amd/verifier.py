@@ -283,6 +283,8 @@ class MultiVerifier(Verifier):
         self.triples: List[Triple] = list(triples or [])
         self.options = set(options)
         self.last_path = None  # "spans", "bits", "committees", "indices" or "points": the key form of the last finish (tests)
+        self.last_each_path = None  # "spans" or "points": the key form of the last verify_each / verify_items
+        self.last_each_status = None  # verify_each on "spans": per set (signature status, key status)
 
     @classmethod
     def from_triples(cls, triples: List[Triple]) -> "MultiVerifier":  # From<Vec<Triple>>
@@ -319,11 +321,11 @@ class MultiVerifier(Verifier):
                                       aggregation_bits, public_keys, signature_kind)
         self.triples.append(t)
 
-    def _finish_spans(self, msgs, sigs, randoms, flags):
-        """The "spans" path, or None when the triples do not qualify: at least one triple came
-        through verify_aggregate_committees, every slot it names keeps exactly the members the triple
-        was built from, and the other triples qualify as for "bits" (a single-committee triple is
-        then a span with one bit)."""
+    def _span_sets(self):
+        """The triples as span sets (base slots, masks, bit strings, index lists), or None when they
+        do not qualify: at least one triple came through verify_aggregate_committees, every slot it
+        names keeps exactly the members the triple was built from, and the other triples qualify as
+        for "bits" (a single-committee triple is then a span with one bit)."""
         spans = [t for t in self.triples if t.span_base is not None]
         if not spans:
             return None
@@ -349,8 +351,15 @@ class MultiVerifier(Verifier):
                 base.append(t.slot), cbits.append(one), fields.append(t.bits), lists.append(())
             else:
                 base.append(None), cbits.append(bytes(8)), fields.append(b""), lists.append(t.indices)
+        return base, cbits, fields, lists
+
+    def _finish_spans(self, msgs, sigs, randoms, flags):
+        """The "spans" path, or None when the triples do not qualify (_span_sets)."""
+        sets = self._span_sets()
+        if sets is None:
+            return None
         self.last_path = "spans"
-        return bls.Signature.multi_verify_compressed_spans(msgs, sigs, base, cbits, fields, lists, randoms, flags)
+        return bls.Signature.multi_verify_compressed_spans(msgs, sigs, *sets, randoms, flags)
 
     def finish(self, randoms=None):
         """verifier.rs:301-323."""
@@ -409,13 +418,48 @@ class MultiVerifier(Verifier):
         check with Signature::verify / fast_aggregate_verify semantics -- the verdict the
         singular path would reach).  A set whose signature does not decode is False.  For a
         caller whose batch failed, so that only the failing items take the singular path
-        (split_failed_batch)."""
+        (split_failed_batch).  Triples that qualify for finish's "spans" path stay in that compact
+        form (gbls_verify_each_spans: no key points uploaded, the cached sums reused; a set whose
+        key the engine rejects is False); last_each_status then keeps every set's (signature
+        status, key status)."""
         if not self.triples:
             return []
+        sets = self._span_sets()
+        if sets is not None:
+            self.last_each_path = "spans"
+            outcomes = bls.Signature.verify_each_spans(
+                [t.message for t in self.triples], [t.signature_bytes for t in self.triples], *sets)
+            self.last_each_status = [(st, kst) for st, kst, _ in outcomes]
+            return [st == 0 and kst == 0 and ok for st, kst, ok in outcomes]
+        self.last_each_path = "points"
+        self.last_each_status = None
         outcomes = bls.Signature.verify_batch_compressed(
             [t.message for t in self.triples], [t.signature_bytes for t in self.triples],
             [t.keys() for t in self.triples])
         return [status == 0 and ok for status, ok in outcomes]
+
+    def verify_items(self, item_of_triple: Iterable[int], randoms=None) -> List[bool]:
+        """Which ITEMS verify, in ONE device submission (gbls_verify_items_spans): triple k belongs
+        to item item_of_triple[k] (nondecreasing, items numbered from 0; an item without a triple
+        is False), and each item is its own random-linear-combination batch -- a gossip aggregate
+        as its three sets, or the blocks of the block verification pool.  For triples that qualify
+        for finish's "spans" path; others are decided set by set over key points (verify_each),
+        an item passing when all of its sets do."""
+        owner = [int(k) for k in item_of_triple]
+        if len(owner) != len(self.triples) or any(a > b for a, b in zip(owner, owner[1:])) or (owner and owner[0] < 0):
+            raise ValueError("one nondecreasing item number per triple")
+        nitems = owner[-1] + 1 if owner else 0
+        offsets = [sum(1 for k in owner if k < s) for s in range(nitems + 1)]
+        if not self.triples:
+            return []
+        sets = self._span_sets()
+        if sets is None:
+            each = self.verify_each()  # last_each_path == "points"
+            return [offsets[s] < offsets[s + 1] and all(each[offsets[s]:offsets[s + 1]]) for s in range(nitems)]
+        self.last_each_path = "spans"
+        flags = 0x1 if VerifierOption.BlockImport in self.options else 0
+        return bls.Signature.verify_items_spans(
+            [t.message for t in self.triples], [t.signature_bytes for t in self.triples], *sets, offsets, randoms, flags)
 
     def has_option(self, option: VerifierOption) -> bool:
         return option in self.options

@@ -1,0 +1,44 @@
+//! Raw bindings of `include/grandine_bls_gpu_each.h`: per-set and per-item verdicts over span
+//! sets, merged across callers.
+//!
+//! Every prototype of that header is declared here with the same name, argument order and meaning
+//! (`tests/test_each_abi.py` parses both files and checks them against each other).  The
+//! conventions of `ffi.rs` hold: status codes mirror `BLST_ERROR`, any device or driver failure is
+//! fail-closed (`GBLS_VERIFY_FAIL`, `gbls_last_error()` set).
+
+use core::ffi::c_int;
+
+extern "C" {
+    pub fn gbls_verify_each_spans(
+        msgs: *const [u8; 32],
+        sigs: *const [u8; 96],
+        com: *const u32,
+        cbits: *const [u8; 8],
+        bits: *const u8,
+        bits_off: *const u32,
+        pk_idx: *const u32,
+        pk_off: *const u32,
+        n: usize,
+        sig_status: *mut i32,
+        key_status: *mut i32,
+        verdicts: *mut i32,
+    ) -> c_int;
+    pub fn gbls_verify_items_spans(
+        msgs: *const [u8; 32],
+        sigs: *const [u8; 96],
+        com: *const u32,
+        cbits: *const [u8; 8],
+        bits: *const u8,
+        bits_off: *const u32,
+        pk_idx: *const u32,
+        pk_off: *const u32,
+        rands: *const u64,
+        n: usize,
+        seg_off: *const u32,
+        nseg: usize,
+        sig_status: *mut i32,
+        key_status: *mut i32,
+        verdicts: *mut i32,
+        call_flags: u32,
+    ) -> c_int;
+}

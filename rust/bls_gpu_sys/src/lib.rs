@@ -22,9 +22,11 @@
 
 pub mod bits;
 pub mod committees;
+pub mod each;
 pub mod ffi;
 pub mod ffi_bits;
 pub mod ffi_committees;
+pub mod ffi_each;
 pub mod ffi_msgcache;
 pub mod ffi_spans;
 pub mod msgcache;

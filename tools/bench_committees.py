@@ -37,9 +37,23 @@ plain single-key sets, the first k members of every committee absent, the forms 
                 gbls_multi_verify_compressed_ex over the points, 64 keys per set
   keys_spans    gbls_g1_aggregate_spans (the keys alone)
 
+With --each the shape is gossip64x3, a failed gossip aggregate batch looked at set by set
+(include/grandine_bls_gpu_each.h): 64 items of three sets, two plain single-key sets (selection
+proof, aggregate-and-proof signature) and one span over 8 committees of 512 members (64 committees
+loaded with their members, item i over committees 8 (i % 8) ..), the first k members of every
+committee absent, one signature bad, the forms alternating:
+
+  each          gbls_verify_each_spans: one verdict per set
+  items         gbls_verify_items_spans: one verdict per item
+  points        gbls_verify_batch_compressed over every participant's key point (what the per-set
+                fallback did before the each call: yardstick a)
+  two           gbls_g1_aggregate_spans, then gbls_verify_batch_compressed over the 192 resulting
+                points: two submissions (yardstick b)
+
   python tools/bench_committees.py                       # both shapes, one JSON line per point
   python tools/bench_committees.py --bits                # ... the aggregation-bit leg
   python tools/bench_committees.py --spans               # the span-set leg (its own shape)
+  python tools/bench_committees.py --each                # per-set and per-item verdicts (its own shape)
   GBLS_COMMITTEE_ROW_MIN=1 python tools/bench_committees.py --tuning --keys-only
 """
 import argparse
@@ -190,6 +204,105 @@ def spans_leg(a, G, F, L, emit, absent_counts):
         emit(res)
 
 
+def each_leg(a, G, F, L, emit, absent_counts):
+    """gossip64x3: the per-set and per-item calls against the two forms available without them."""
+    nitem, per_set, size, ncom = 64, 8, 512, 64
+    n, nreg = 3 * nitem, ncom * size
+    seed = b"bench-committees/gossip64x3"
+    sks, comp = F.registry(nreg, seed)
+    if F.load_registry(comp).any():
+        raise SystemExit("registry load failed")
+    perm, off = F.committees(nreg, ncom, 7)
+    ptr = lambda x: x.ctypes.data_as(ctypes.c_void_p)
+    perm_c = np.ascontiguousarray(perm, dtype=np.uint32)
+    off_c = np.ascontiguousarray(off, dtype=np.uint32)
+    st = G.i32_array(ncom)
+    rc = L.gbls_committees_set_members(0, ptr(perm_c), ptr(off_c), ncom, st)
+    if rc != G.SUCCESS or any(st[c] for c in range(ncom)):
+        raise SystemExit("gbls_committees_set_members rc=%d" % rc)
+    emit({"shape": "gossip64x3", "sets": n, "items": nitem, "committees_per_span": per_set, "size": size,
+          "registry": nreg})
+    raw = F.public_keys(sks)
+    pk = np.frombuffer(raw, dtype=np.uint8).reshape(nreg, 96)
+    sk = np.array(sks, dtype=object)
+    totals = [int(sum(sk[perm[off[c]:off[c + 1]]])) for c in range(ncom)]
+    msgs = F.messages(n, seed)
+    rands = (ctypes.c_uint64 * n)(*F.rands(n, n + size))
+    seg = np.arange(0, n + 1, 3, dtype=np.uint32)
+    bad_item = 17
+    for k in absent_counts:
+        # set 3 i, 3 i + 1: a single key; set 3 i + 2: the span over committees 8 (i % 8) .. + 7
+        singles = [int(perm[off[(5 * j) % ncom] + k + j % 7]) for j in range(2 * nitem)]
+        sums, lists = [], []
+        for i in range(nitem):
+            first = per_set * (i % 8)
+            t = sum(totals[c] - int(sum(sk[perm[off[c]:off[c] + k]])) for c in range(first, first + per_set))
+            sums += [sks[singles[2 * i]], sks[singles[2 * i + 1]], t % F.R_ORDER]
+            lists += [np.array([singles[2 * i]]), np.array([singles[2 * i + 1]]),
+                      np.concatenate([perm[off[c] + k:off[c + 1]] for c in range(first, first + per_set)])]
+        sigs = F.sign(sums, msgs)
+        sig_c = ctypes.create_string_buffer(96 * n)
+        G.check(L.gbls_g2_compress(sigs, n, sig_c), "gbls_g2_compress")
+        b = 96 * (3 * bad_item + 2)  # one bad signature: a valid signature of another set
+        sig_c[b:b + 96] = sig_c.raw[96 * 2:96 * 3]
+        base = np.full(n, G.NO_COMMITTEE, dtype=np.uint32)
+        base[2::3] = [per_set * (i % 8) for i in range(nitem)]
+        masks = np.zeros((n, 8), dtype=np.uint8)
+        masks[2::3, 0] = 0xFF
+        bits = np.zeros(8 * (per_set * size // 8 + 1), dtype=np.uint8)
+        for c in range(per_set):
+            bits[c * size + k:(c + 1) * size] = 1
+        bits[per_set * size] = 1  # the delimiter
+        field = np.packbits(bits, bitorder="little").tobytes()
+        s_all = ctypes.create_string_buffer(field * nitem, len(field) * nitem)
+        s_off = np.zeros(n + 1, dtype=np.uint32)
+        s_off[1:] = len(field) * ((np.arange(1, n + 1)) // 3)
+        q_idx = np.ascontiguousarray(singles, dtype=np.uint32)
+        q_off = np.zeros(n + 1, dtype=np.uint32)
+        q_off[1:] = [2 * (j // 3) + min(j % 3, 2) for j in range(1, n + 1)]
+        l_idx = np.concatenate(lists)
+        l_off = np.zeros(n + 1, dtype=np.uint32)
+        l_off[1:] = np.cumsum([len(v) for v in lists])
+        l_pts = np.ascontiguousarray(pk[l_idx])
+        keys_out = ctypes.create_string_buffer(96 * n)
+        sst, kst, v = G.i32_array(n), G.i32_array(n), G.i32_array(n)
+        span_args = 4 * n + 8 * n + 4 * (n + 1) + int(s_off[n]) + 4 * len(singles) + 4 * (n + 1)
+        upload = {"each": span_args, "items": span_args + 8 * n + 4 * (nitem + 1),
+                  "points": 4 * (n + 1) + 96 * int(l_off[n]), "two": span_args + 96 * n}
+        want = [int(j != 3 * bad_item + 2) for j in range(n)]
+
+        def call(which):
+            t0 = time.perf_counter()
+            if which == "each":
+                rc = L.gbls_verify_each_spans(msgs, sig_c, ptr(base), ptr(masks), s_all, ptr(s_off), ptr(q_idx),
+                                              ptr(q_off), n, sst, kst, v)
+            elif which == "items":
+                rc = L.gbls_verify_items_spans(msgs, sig_c, ptr(base), ptr(masks), s_all, ptr(s_off), ptr(q_idx),
+                                               ptr(q_off), rands, n, ptr(seg), nitem, sst, kst, v, 0)
+            elif which == "points":
+                rc = L.gbls_verify_batch_compressed(msgs, sig_c, ptr(l_pts), ptr(l_off), n, sst, v)
+            else:
+                rc = L.gbls_g1_aggregate_spans(ptr(base), ptr(masks), s_all, ptr(s_off), ptr(q_idx), ptr(q_off), n,
+                                               keys_out, kst)
+                if rc == G.SUCCESS:
+                    rc = L.gbls_verify_batch_compressed(msgs, sig_c, keys_out, None, n, sst, v)
+            dt = time.perf_counter() - t0
+            m = nitem if which == "items" else n
+            good = [int(v[j] == G.SUCCESS) for j in range(m)]
+            if rc != G.SUCCESS or good != ([int(i != bad_item) for i in range(nitem)] if which == "items" else want):
+                raise SystemExit("gossip64x3 absent=%d %s: rc=%d err=%d failing=%s" % (
+                    k, which, rc, L.gbls_last_error(), [j for j in range(m) if not good[j]]))
+            return dt
+
+        kinds = ["each", "items", "points", "two"]
+        f, calls = timed(call, kinds, a.warmup, a.window, a.runs)
+        res = {"shape": "gossip64x3", "sets": n, "absent": k, "calls_per_run": calls, "upload_bytes": upload}
+        for kind in kinds:
+            res[kind] = summary(f[kind])
+            res[kind]["runs_us"] = [round(x, 1) for x in f[kind]]
+        emit(res)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--runs", type=int, default=5)
@@ -203,6 +316,9 @@ def main():
                     help="the aggregation-bit calls beside the two committees forms, full calls and keys alone")
     ap.add_argument("--spans", action="store_true",
                     help="the span-set leg: block8x64x512 through the spans call and the two forms without it")
+    ap.add_argument("--each", action="store_true",
+                    help="the per-set / per-item leg: gossip64x3 through the each and items calls and the two forms "
+                         "without them")
     ap.add_argument("--out", default="", help="also append the JSON lines to this file")
     ap.add_argument("--tuning", action="store_true", help="let the engine read its GBLS_* tuning variables")
     a = ap.parse_args()
@@ -223,8 +339,10 @@ def main():
 
     if a.spans:
         spans_leg(a, G, F, L, emit, [int(x) for x in a.absent.split(",")] if a.absent else [0, 5, 51, 256])
+    if a.each:
+        each_leg(a, G, F, L, emit, [int(x) for x in a.absent.split(",")] if a.absent else [0, 5, 51])
     for name, ncom, size in SHAPES:
-        if a.spans or (want and name not in want):
+        if a.spans or a.each or (want and name not in want):
             continue
         nreg = ncom * size
         seed = b"bench-committees/" + name.encode()
