@@ -127,6 +127,13 @@ EXPORTS_EACH = [
     "gbls_verify_each_spans",
     "gbls_verify_items_spans",
 ]
+# include/grandine_bls_gpu_local.h (local key sets: compressed keys decoded inside the submission)
+EXPORTS_LOCAL = [
+    "gbls_g1_aggregate_local",
+    "gbls_verify_each_local",
+    "gbls_verify_items_local",
+]
+LOCAL_KEYS = 0xFFFFFFFE  # GBLS_LOCAL_KEYS: com[i] of a local set
 # include/grandine_bls_gpu_msgcache.h (message line cache)
 EXPORTS_MSGCACHE = [
     "gbls_msgcache_configure",
@@ -238,6 +245,11 @@ def load_library():
                 "gbls_verify_each_spans": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
                 "gbls_verify_items_spans": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz,
                                                        _vp, _vp, _vp, _c.c_uint32]),
+                "gbls_g1_aggregate_local": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp]),
+                "gbls_verify_each_local": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp,
+                                                      _vp, _vp]),
+                "gbls_verify_items_local": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp,
+                                                       _sz, _vp, _vp, _vp, _vp, _c.c_uint32]),
                 "gbls_msgcache_configure": (_c.c_int, [_sz]),
                 "gbls_msgcache_slots": (_sz, []),
                 "gbls_msgcache_clear": (_c.c_int, []),
@@ -245,10 +257,10 @@ def load_library():
             }
             for name, (res, args) in sig.items():
                 # an experiment build (GBLS_LIB) may predate the message line cache, the bits, the
-                # spans or the each calls: A/B tools load it and leave those entries alone; the
-                # package's own library must have them
+                # spans, the each or the local calls: A/B tools load it and leave those entries
+                # alone; the package's own library must have them
                 if (_override and name in EXPORTS_MSGCACHE + EXPORTS_BITS + EXPORTS_SPANS + EXPORTS_EACH
-                        and not hasattr(lib, name)):
+                        + EXPORTS_LOCAL and not hasattr(lib, name)):
                     continue
                 fn = getattr(lib, name)
                 fn.restype = res

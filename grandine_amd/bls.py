@@ -483,6 +483,63 @@ class Signature:
         return (verdicts, [(st[i], kst[i]) for i in range(n)]) if with_statuses else verdicts
 
     @staticmethod
+    def _local_table(local_keys):
+        """A call's local key table as the C arguments (pkb, npkb)."""
+        keys = [bytes(k) for k in local_keys]
+        if any(len(k) != 48 for k in keys):
+            raise ValueError("local keys are 48 compressed bytes")
+        return (G.buf(b"".join(keys)) if keys else None), len(keys)
+
+    @staticmethod
+    def verify_each_local(messages: Iterable[bytes], signature_bytes: Iterable[bytes], base_slots: Iterable[int],
+                          committee_bits: Iterable[bytes], bitfields: Iterable[bytes],
+                          validator_indices: Iterable[Sequence[int]], local_keys: Iterable[bytes]):
+        """verify_each_spans with a call-local table of compressed keys (gbls_verify_each_local): a
+        set whose base slot is ``G.LOCAL_KEYS`` sums the keys ``local_keys[p]`` for the positions p
+        of ``validator_indices[i]``; the keys are decoded on the device inside the same submission.
+        Returns (per set (signature status, key status, ok), per local key its decoding status)."""
+        args, n = Signature._span_sets(messages, signature_bytes, base_slots, committee_bits, bitfields,
+                                       validator_indices)
+        pkb, npkb = Signature._local_table(local_keys)
+        if n == 0 and npkb == 0:
+            return [], []
+        L = G.lib()
+        st, kst, v, pst = G.i32_array(n), G.i32_array(n), G.i32_array(n), G.i32_array(npkb)
+        G.check(L.gbls_verify_each_local(*args, pkb, npkb, n, st, kst, v, pst), "gbls_verify_each_local")
+        return [(st[i], kst[i], v[i] == G.SUCCESS) for i in range(n)], [pst[j] for j in range(npkb)]
+
+    @staticmethod
+    def verify_items_local(messages: Iterable[bytes], signature_bytes: Iterable[bytes], base_slots: Iterable[int],
+                           committee_bits: Iterable[bytes], bitfields: Iterable[bytes],
+                           validator_indices: Iterable[Sequence[int]], local_keys: Iterable[bytes],
+                           item_offsets: Sequence[int], randoms: Sequence[int] = None, call_flags: int = 0,
+                           with_statuses: bool = False):
+        """verify_items_spans with a call-local table of compressed keys (gbls_verify_items_local;
+        local sets as in verify_each_local).  Returns one bool per item; with_statuses: (those, per
+        set (signature status, key status), per local key its decoding status)."""
+        args, n = Signature._span_sets(messages, signature_bytes, base_slots, committee_bits, bitfields,
+                                       validator_indices)
+        pkb, npkb = Signature._local_table(local_keys)
+        seg = [int(o) for o in item_offsets]
+        nseg = len(seg) - 1
+        if nseg < 0 or seg[0] != 0 or seg[-1] != n or any(a > b for a, b in zip(seg, seg[1:])):
+            raise ValueError("item offsets run from 0 to the number of sets, nondecreasing")
+        if (n == 0 or nseg == 0) and npkb == 0:
+            return ([False] * nseg, [], []) if with_statuses else [False] * nseg
+        if randoms is None:
+            randoms = [secrets.randbits(64) or 1 for _ in range(n)]
+        if len(randoms) != n:
+            raise ValueError("one scalar per set")
+        L = G.lib()
+        st, kst, v, pst = G.i32_array(n), G.i32_array(n), G.i32_array(nseg), G.i32_array(npkb)
+        G.check(L.gbls_verify_items_local(*args, pkb, npkb, G.u64_array(randoms), n, G.u32_array(seg), nseg, st, kst,
+                                          v, pst, call_flags), "gbls_verify_items_local")
+        verdicts = [v[s] == G.SUCCESS for s in range(nseg)]
+        if not with_statuses:
+            return verdicts
+        return verdicts, [(st[i], kst[i]) for i in range(n)], [pst[j] for j in range(npkb)]
+
+    @staticmethod
     def verify_batch_compressed(messages: Iterable[bytes], signature_bytes: Iterable[bytes],
                                 public_keys: Iterable) -> List:
         """SingleVerifier::extend's try_from + verify per triple (verifier.rs:215-236) as ONE

@@ -39,6 +39,7 @@
 #include "../../include/grandine_bls_gpu_bits.h"
 #include "../../include/grandine_bls_gpu_each.h"
 #include "../../include/grandine_bls_gpu_spans.h"
+#include "../../include/grandine_bls_gpu_local.h"
 #include "gbls_common.h"
 #include "gbls_bits.h"
 #include "gbls_committees.h"
@@ -47,6 +48,7 @@
 #include "gbls_msgcache.h"
 #include "gbls_sched.h"
 #include "gbls_spans.h"
+#include "gbls_local.h"
 #include "gbls_tables.h"
 
 using namespace gbls;
@@ -255,7 +257,7 @@ struct Ctx {
   bool used = false;                  // last_stream is meaningful
   hipStream_t last_stream = nullptr;  // main stream of the previous call
   Buf in0, in1, in2, in3, in4, in5, U, Q, H, P, Pc, R, Sj, gpart, lines, Ts, V0, V1, V28, hparts, tab, part, err, out0,
-      out1, pks, pre, pre2, msm, sigd, sigst, rnd, ng1, gerr, gv, redo, rtab, in6, Pset, in7, in8, spj, spf;
+      out1, pks, pre, pre2, msm, sigd, sigst, rnd, ng1, gerr, gv, redo, rtab, in6, Pset, in7, in8, spj, spf, in9, loc, locst;
   // per-call option of the next pipeline_partials on this lease: compressed signatures
   // (96 B each, device) to decompress on the signature-side stream into `sigs`, with their
   // BLST_ERROR statuses (device) failing their segments (consumed and reset by the pipeline)
@@ -849,9 +851,17 @@ bool resolve_pks(Ctx &c, Device &d, const PkSource &src, size_t n, hipStream_t s
   if (src.span_sets) {  // span sets: a contribution per (set, committee) piece, folded per set (k_spans.hip)
     const size_t np = src.span_np;
     if (!c.ensure(c.spj, np * sizeof(g1j) + 16) || !c.ensure(c.spf, np * 4 + 16)) return false;
-    launch_g1_span_keys(st, reg, (uint32_t)g.reg_n, d.com.as<g1a>(), (uint32_t)g.com_n, src.span_pieces,
-                        src.span_sets, src.bit_rows, src.span_np, (uint32_t)n, src.max_len, src.span_max_pieces,
-                        c.spj.p, c.spf.as<uint32_t>(), c.pks.as<g1a>(), c.pre.as<int32_t>());
+    if (src.local) {  // local key sets: the call's table decoded, then read by the tail pieces (k_local.hip)
+      launch_g1_local_decode(st, src.loc_in, (uint32_t)src.npkb, const_cast<g1a *>(src.loc), src.loc_st);
+      launch_g1_span_keys_local(st, reg, (uint32_t)g.reg_n, d.com.as<g1a>(), (uint32_t)g.com_n, src.loc,
+                                (uint32_t)src.npkb, src.span_pieces, src.span_sets, src.bit_rows, src.span_np,
+                                src.loc_np, (uint32_t)n, src.max_len, src.loc_max_len, src.span_max_pieces, c.spj.p,
+                                c.spf.as<uint32_t>(), c.pks.as<g1a>(), c.pre.as<int32_t>());
+    } else {
+      launch_g1_span_keys(st, reg, (uint32_t)g.reg_n, d.com.as<g1a>(), (uint32_t)g.com_n, src.span_pieces,
+                          src.span_sets, src.bit_rows, src.span_np, (uint32_t)n, src.max_len, src.span_max_pieces,
+                          c.spj.p, c.spf.as<uint32_t>(), c.pks.as<g1a>(), c.pre.as<int32_t>());
+    }
   } else if (src.bit_sets)  // resident members chosen by aggregation bits (member blocks: read as the registry is)
     launch_g1_bits_keys(st, reg, (uint32_t)g.reg_n, d.com.as<g1a>(), (uint32_t)g.com_n, src.bit_sets,
                         src.bit_rows, (uint32_t)n, src.max_len, c.pks.as<g1a>(), c.pre.as<int32_t>());
@@ -1417,16 +1427,31 @@ bool upload_bit_sets(Ctx &c, Device &d, const PkSource &host, size_t b, size_t e
 // Span sets [b, e) (gbls_spans.h): the plain sets' index lists, one SpanSet per set, one SpanPiece
 // per (set, named committee) pair or plain list (members resolved from Engine::mem to d's block
 // memory; the caller holds the registry lock) and this shard's slice of the bit strings, repacked
-// to word-aligned rows.  The call's piece count fits 32 bits (spans_args_ok).
+// to word-aligned rows.  The call's piece count fits 32 bits (spans_args_ok).  A local source
+// (gbls_local.h): the WHOLE key table goes up with every shard, the local sets' pieces (their
+// positions, from the same index lists) are laid in the tail of the piece array.
 bool upload_span_sets(Ctx &c, Device &d, const PkSource &host, size_t b, size_t e, hipStream_t st, PkSource *dev) {
   const size_t n = e - b;
   const uint32_t base = host.off ? host.off[b] : 0, cnt = host.off ? host.off[e] - base : 0;
   if (!c.upload_staged(c.in2, cnt ? host.idx + base : nullptr, (size_t)cnt * 4, st)) return false;
-  size_t nw = 0, np = 0;
-  for (size_t i = b; i < e; i++) {
-    nw += bits_row_words(host.bits_off[i + 1] - host.bits_off[i]);
-    np += host.com[i] == kNoCommittee ? 1 : span_mask_count(host.cbits[i]);
+  size_t nw = 0;
+  for (size_t i = b; i < e; i++) nw += bits_row_words(host.bits_off[i + 1] - host.bits_off[i]);
+  // where each set's pieces start: in set order, or (a local source) the local sets' in the tail
+  std::vector<uint32_t> &first = c.host_tab;
+  first.assign(n, 0);
+  LocalLayout lay;
+  if (host.local) {
+    if (!local_layout(host.com, host.cbits, b, e, first.data(), &lay)) return fail(GBLS_ERR_ARG);
+    if (!c.upload_staged(c.in9, host.npkb ? &host.pkb[0][0] : nullptr, 48 * host.npkb, st) ||
+        !c.ensure(c.loc, host.npkb * sizeof(g1a) + 16) || !c.ensure(c.locst, host.npkb * 4 + 16))
+      return false;
+  } else {
+    for (size_t i = 0; i < n; i++) {
+      first[i] = lay.np_span;
+      lay.np_span += host.com[b + i] == kNoCommittee ? 1 : span_mask_count(host.cbits[b + i]);
+    }
   }
+  const size_t np = (size_t)lay.np_span + lay.np_local;
   // built in the call's pinned staging buffer itself, as upload_bit_sets does
   const size_t sets_bytes = (n * sizeof(SpanSet) + 7) & ~(size_t)7, pieces_bytes = np * sizeof(SpanPiece),
                rows_bytes = (nw + 1) * 4;
@@ -1445,23 +1470,18 @@ bool upload_span_sets(Ctx &c, Device &d, const PkSource &host, size_t b, size_t 
     *len = v.len;
     return true;
   };
-  uint32_t w = 0, q = 0;
+  uint32_t w = 0;
   for (size_t i = 0; i < n; i++) {
     SpanSet &s = sets[i];
-    s.first = q;
+    const uint32_t q = s.first = first[i];
     s.npieces = s.row = s.nbytes = s.M = 0;
-    if (host.com[b + i] == kNoCommittee) {
-      SpanPiece &p = pieces[q++];
-      p.list = nullptr;
-      p.cnt = p.bit = 0;
-      p.slot = kNoCommittee;
-      p.set = (uint32_t)i;
-      if (host.off) {
-        p.list = c.in2.as<uint32_t>() + (host.off[b + i] - base);
-        p.cnt = host.off[b + i + 1] - host.off[b + i];
-      }
+    const bool local = host.local && host.com[b + i] == kLocalKeys;
+    if (local || host.com[b + i] == kNoCommittee) {
+      SpanPiece &p = pieces[q];
+      local_list_piece(p, (uint32_t)i, c.in2.as<uint32_t>(), host.off, b, b + i);
       s.npieces = 1;
-      dev->max_len = std::max(dev->max_len, p.cnt);
+      uint32_t &longest = local ? dev->loc_max_len : dev->max_len;
+      longest = std::max(longest, p.cnt);
       continue;
     }
     s.nbytes = host.bits_off[b + i + 1] - host.bits_off[b + i];
@@ -1471,7 +1491,6 @@ bool upload_span_sets(Ctx &c, Device &d, const PkSource &host, size_t b, size_t 
     s.npieces = span_pieces((uint32_t)i, host.com[b + i], host.cbits[b + i], members, &pieces[q], &s.M);
     for (uint32_t k = 0; k < s.npieces; k++)
       dev->max_len = std::max(dev->max_len, span_work(&rows[s.row], s.nbytes, pieces[q + k].bit, pieces[q + k].cnt));
-    q += s.npieces;
     dev->span_max_pieces = std::max(dev->span_max_pieces, s.npieces);
   }
   if (!c.send_staged(c.in5.p, sets, sets_bytes, st) || !c.send_staged(c.in8.p, pieces, pieces_bytes, st) ||
@@ -1480,8 +1499,16 @@ bool upload_span_sets(Ctx &c, Device &d, const PkSource &host, size_t b, size_t 
   dev->idx = c.in2.as<uint32_t>();
   dev->span_sets = c.in5.p;
   dev->span_pieces = c.in8.p;
-  dev->span_np = q;
+  dev->span_np = (uint32_t)np;
   dev->bit_rows = c.in7.as<uint32_t>();
+  if (host.local) {
+    dev->local = true;
+    dev->npkb = host.npkb;
+    dev->loc_in = c.in9.as<uint8_t>();
+    dev->loc = c.loc.as<g1a>();
+    dev->loc_st = c.locst.as<int32_t>();
+    dev->loc_np = lay.np_local;
+  }
   return true;
 }
 
@@ -1594,7 +1621,7 @@ bool enqueue_host_batch(Ctx &c, Device &d, const uint8_t *msgs, const g2a *sigs,
                         const uint8_t *sigs_c, int32_t *sig_status, const PkSource &src,
                         const uint64_t *rands, size_t b, size_t e, const uint32_t *seg,
                         size_t nseg, int32_t *verdicts, fp12 *part_dst, int32_t *err_dst,
-                        int dst_dev, int32_t *key_status = nullptr) {
+                        int dst_dev, int32_t *key_status = nullptr, int32_t *pkb_status = nullptr) {
   hipStream_t st = c.own;
   size_t n = e - b;
   if (key_status && !src.cbits) return fail(GBLS_ERR_ARG);  // the statuses of a span source only
@@ -1675,6 +1702,10 @@ bool enqueue_host_batch(Ctx &c, Device &d, const uint8_t *msgs, const g2a *sigs,
   // a span source's keys are always resolved (resolve_pks, side stream 1, joined before the Miller
   // product): this shard's slice of their statuses
   if (key_status && n) HIPCHK(hipMemcpyAsync(key_status + b, c.pre.p, n * 4, hipMemcpyDeviceToHost, st));
+  // a local source's table is decoded whole by every shard: its statuses are copied back once, by
+  // the shard that holds the call's first set
+  if (pkb_status && src.npkb && n && b == 0)
+    HIPCHK(hipMemcpyAsync(pkb_status, c.locst.p, src.npkb * 4, hipMemcpyDeviceToHost, st));
   return true;
 }
 
@@ -1684,7 +1715,8 @@ bool enqueue_host_batch(Ctx &c, Device &d, const uint8_t *msgs, const g2a *sigs,
 // only): every set's key status, each shard writing its slice.
 bool verify_host(const uint8_t *msgs, const g2a *sigs, const uint8_t *sigs_c, int32_t *sig_status,
                  const PkSource &src, const uint64_t *rands, size_t n, const uint32_t *seg_off,
-                 size_t nseg, int32_t *verdicts, int cls = 0, int32_t *key_status = nullptr) {
+                 size_t nseg, int32_t *verdicts, int cls = 0, int32_t *key_status = nullptr,
+                 int32_t *pkb_status = nullptr) {
   std::shared_lock<std::shared_mutex> rl(g.reg_mu);
   const size_t ndev = g.devs.size();
   // ---- one large batch: per-device Miller partials, gathered device-to-device onto device 0
@@ -1713,7 +1745,7 @@ bool verify_host(const uint8_t *msgs, const g2a *sigs, const uint8_t *sigs_c, in
       uint32_t seg[2] = {0, (uint32_t)(e - b)};
       ok = L.ok() && enqueue_host_batch(*L, d, msgs, sigs, sigs_c, sig_status, src, rands, b, e,
                                         seg, 1, nullptr, L0->part.as<fp12>() + j,
-                                        L0->err.as<int32_t>() + j, d0.hipdev, key_status);
+                                        L0->err.as<int32_t>() + j, d0.hipdev, key_status, pkb_status);
       if (!ok) break;
       hipEvent_t ev;
       if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
@@ -1765,7 +1797,7 @@ bool verify_host(const uint8_t *msgs, const g2a *sigs, const uint8_t *sigs_c, in
     Lease &L = *leases.back();
     ok = L.ok() && enqueue_host_batch(*L, d, msgs, sigs, sigs_c, sig_status, src, rands, b, e,
                                       segs[j].data(), s1 - s0, verdicts + s0, nullptr, nullptr, 0,
-                                      key_status);
+                                      key_status, pkb_status);
   }
   rl.unlock();  // enqueued: the host waits do not hold up registry updates
   for (auto &L : leases)
@@ -1800,7 +1832,7 @@ bool coalesced_verify(CoReq &r) {
   if (g.block_hold) cfg.hold = &g.block_active;
   bool ok = co.submit(r, cfg, [](CoReq &m) {
     m.ok = verify_host(m.msgs, m.sigs, m.sigs_c, m.sig_status, m.src, m.rands, m.n, m.seg_off,
-                       m.nseg, m.verdicts, m.prio, m.key_status);
+                       m.nseg, m.verdicts, m.prio, m.key_status, m.pkb_status);
     m.err = t_last_error;  // the leader's thread-local code, handed to every merged caller
   });
   t_last_error = r.err;
@@ -3131,6 +3163,141 @@ int gbls_verify_items_spans(const uint8_t (*msgs)[32], const uint8_t (*sigs)[96]
                             int32_t *verdicts, uint32_t call_flags) {
   return spans_checks_co(msgs, sigs, com, cbits, bits, bits_off, pk_idx, pk_off, rands, n, seg_off, nseg,
                          sig_status, key_status, verdicts, call_flags, false);
+}
+
+// ---- local key sets (include/grandine_bls_gpu_local.h): the span calls with a call-local table of
+// compressed keys, decoded inside the submission (k_local.hip), and a third kind of set that sums
+// positions of that table.
+static_assert(GBLS_LOCAL_KEYS == kLocalKeys && kLocalKeys == sched::kLocalSet, "one value for a local set's slot");
+
+static void local_source(PkSource &src, const uint32_t *com, const uint8_t (*cbits)[8], const uint8_t *bits,
+                         const uint32_t *bits_off, const uint32_t *pk_idx, const uint32_t *pk_off,
+                         const uint8_t (*pkb)[48], size_t npkb) {
+  src.com = com;
+  src.cbits = cbits;
+  src.bits = bits;
+  src.bits_off = bits_off;
+  src.idx = pk_idx;
+  src.off = pk_off;
+  src.local = true;
+  src.pkb = pkb;
+  src.npkb = npkb;
+}
+
+int gbls_g1_aggregate_local(const uint32_t *com, const uint8_t (*cbits)[8], const uint8_t *bits,
+                            const uint32_t *bits_off, const uint32_t *pk_idx, const uint32_t *pk_off,
+                            const uint8_t (*pkb)[48], size_t npkb, size_t n, gbls_p1_affine *out, int32_t *status,
+                            int32_t *pkb_status) {
+  const bool table_ok = (uint64_t)npkb <= 0xffffffffull;  // (a count that does not fit names no array to fill)
+  auto prefill = [&] {
+    fill(status, n, GBLS_BAD_ENCODING);
+    if (out) std::memset(out, 0, n * sizeof(*out));
+    if (pkb_status && table_ok) fill(pkb_status, npkb, GBLS_BAD_ENCODING);
+  };
+  prefill();
+  API_BEGIN
+  if (!table_ok || (npkb && !pkb)) return fail(GBLS_ERR_ARG), FAILED;
+  if (n == 0 && npkb == 0) return GBLS_SUCCESS;
+  if (n && (!out || !local_args_ok(com, cbits, bits, bits_off, pk_idx, pk_off, pkb, npkb, n)))
+    return fail(GBLS_ERR_ARG), FAILED;
+  PkSource src, dsrc;
+  local_source(src, com, cbits, bits, bits_off, pk_idx, pk_off, pkb, npkb);
+  std::shared_lock<std::shared_mutex> rl(g.reg_mu);
+  Device &d = pick_device();
+  Lease L(d);
+  Ctx &c = *L;
+  hipStream_t st = c.own;
+  const g1a *keys = nullptr;
+  const int32_t *pre = nullptr;
+  if (!L.ok() || !c.begin(st)) return FAILED;
+  if (n == 0) {  // a table without sets: its keys are decoded all the same
+    if (!c.upload_staged(c.in9, &pkb[0][0], 48 * npkb, st) || !c.ensure(c.loc, npkb * sizeof(g1a) + 16) ||
+        !c.ensure(c.locst, npkb * 4 + 16))
+      return FAILED;
+    launch_g1_local_decode(st, c.in9.as<uint8_t>(), (uint32_t)npkb, c.loc.as<g1a>(), c.locst.as<int32_t>());
+  } else {
+    if (!upload_pks(c, src, 0, n, st, &dsrc, &d) || !resolve_pks(c, d, dsrc, n, st, &keys, &pre)) return FAILED;
+    if (hipMemcpyAsync(out, keys, n * sizeof(g1a), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(status, pre, n * 4, hipMemcpyDeviceToHost, st) != hipSuccess)
+      return fail(GBLS_ERR_HIP), FAILED;
+  }
+  if (pkb_status && npkb &&
+      hipMemcpyAsync(pkb_status, c.locst.p, npkb * 4, hipMemcpyDeviceToHost, st) != hipSuccess)
+    return fail(GBLS_ERR_HIP), FAILED;
+  rl.unlock();  // enqueued: the host wait below does not hold up registry updates
+  if (hipStreamSynchronize(st) != hipSuccess) {
+    prefill();
+    return fail(GBLS_ERR_HIP), FAILED;
+  }
+  return GBLS_SUCCESS;
+}
+
+// both verify calls: spans_checks_co's request with the key table, a kind of its own in the coalescer
+static int local_checks_co(const uint8_t (*msgs)[32], const uint8_t (*sigs)[96], const uint32_t *com,
+                           const uint8_t (*cbits)[8], const uint8_t *bits, const uint32_t *bits_off,
+                           const uint32_t *pk_idx, const uint32_t *pk_off, const uint8_t (*pkb)[48], size_t npkb,
+                           const uint64_t *rands, size_t n, const uint32_t *seg_off, size_t nseg, int32_t *sig_status,
+                           int32_t *key_status, int32_t *verdicts, int32_t *pkb_status, uint32_t call_flags,
+                           bool each) {
+  const bool table_ok = (uint64_t)npkb <= 0xffffffffull;
+  auto prefill = [&] {
+    if (verdicts) fill(verdicts, nseg, GBLS_VERIFY_FAIL);
+    if (sig_status) fill(sig_status, n, GBLS_BAD_ENCODING);
+    if (key_status) fill(key_status, n, GBLS_BAD_ENCODING);
+    if (pkb_status && table_ok) fill(pkb_status, npkb, GBLS_BAD_ENCODING);
+  };
+  prefill();
+  API_BEGIN
+  if (!table_ok || (npkb && !pkb)) return fail(GBLS_ERR_ARG), FAILED;
+  if (n == 0 || nseg == 0) {  // no set names the table: decoded for its statuses alone
+    if (npkb && pkb_status)
+      return gbls_g1_aggregate_local(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, pkb, npkb, 0, nullptr,
+                                     nullptr, pkb_status);
+    return GBLS_SUCCESS;
+  }
+  if (!msgs || !sigs || !sig_status || !key_status || !verdicts ||
+      !local_args_ok(com, cbits, bits, bits_off, pk_idx, pk_off, pkb, npkb, n))
+    return fail(GBLS_ERR_ARG), FAILED;
+  std::vector<uint32_t> ident;
+  if (each) {  // independent checks: one segment per set
+    ident.resize(n + 1);
+    for (size_t i = 0; i <= n; i++) ident[i] = (uint32_t)i;
+    seg_off = ident.data();
+  } else if (!rands || !valid_offsets(seg_off, nseg, n)) {
+    return fail(GBLS_ERR_ARG), FAILED;
+  }
+  CoReq r{&msgs[0][0], nullptr, PkSource(), rands, n, seg_off, nseg, verdicts};
+  local_source(r.src, com, cbits, bits, bits_off, pk_idx, pk_off, pkb, npkb);
+  r.sigs_c = &sigs[0][0];
+  r.sig_status = sig_status;
+  r.key_status = key_status;
+  r.pkb_status = pkb_status;
+  r.prio = (call_flags & GBLS_CALL_BLOCK) ? 1 : 0;
+  BlockActive block_active(r.prio != 0);
+  if (!coalesced_verify(r)) {
+    prefill();
+    return FAILED;
+  }
+  return GBLS_SUCCESS;
+}
+
+int gbls_verify_each_local(const uint8_t (*msgs)[32], const uint8_t (*sigs)[96], const uint32_t *com,
+                           const uint8_t (*cbits)[8], const uint8_t *bits, const uint32_t *bits_off,
+                           const uint32_t *pk_idx, const uint32_t *pk_off, const uint8_t (*pkb)[48], size_t npkb,
+                           size_t n, int32_t *sig_status, int32_t *key_status, int32_t *verdicts,
+                           int32_t *pkb_status) {
+  return local_checks_co(msgs, sigs, com, cbits, bits, bits_off, pk_idx, pk_off, pkb, npkb, nullptr, n, nullptr, n,
+                         sig_status, key_status, verdicts, pkb_status, 0, true);
+}
+
+int gbls_verify_items_local(const uint8_t (*msgs)[32], const uint8_t (*sigs)[96], const uint32_t *com,
+                            const uint8_t (*cbits)[8], const uint8_t *bits, const uint32_t *bits_off,
+                            const uint32_t *pk_idx, const uint32_t *pk_off, const uint8_t (*pkb)[48], size_t npkb,
+                            const uint64_t *rands, size_t n, const uint32_t *seg_off, size_t nseg,
+                            int32_t *sig_status, int32_t *key_status, int32_t *verdicts, int32_t *pkb_status,
+                            uint32_t call_flags) {
+  return local_checks_co(msgs, sigs, com, cbits, bits, bits_off, pk_idx, pk_off, pkb, npkb, rands, n, seg_off, nseg,
+                         sig_status, key_status, verdicts, pkb_status, call_flags, false);
 }
 
 // ---- message line cache (include/grandine_bls_gpu_msgcache.h).  None of these needs a device:

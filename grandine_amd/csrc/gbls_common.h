@@ -112,6 +112,17 @@ void launch_g1_span_keys(hipStream_t st, const g1a *reg, uint32_t nreg, const g1
                          const void *pieces, const void *sets, const uint32_t *rows, uint32_t np, uint32_t n,
                          uint32_t max_work, uint32_t max_pieces, void *contrib, uint32_t *pflags, g1a *out,
                          int32_t *status);
+// the same over a piece array whose tail [np - np_local, np) holds local key sets' pieces
+// (gbls_local.h): the piece kernel runs over the head with the registry and over the tail with
+// the call's table loc[nloc], each range in the form its own longest piece asks for
+void launch_g1_span_keys_local(hipStream_t st, const g1a *reg, uint32_t nreg, const g1a *tab, uint32_t ntab,
+                               const g1a *loc, uint32_t nloc, const void *pieces, const void *sets,
+                               const uint32_t *rows, uint32_t np, uint32_t np_local, uint32_t n, uint32_t max_work,
+                               uint32_t max_work_local, uint32_t max_pieces, void *contrib, uint32_t *pflags,
+                               g1a *out, int32_t *status);
+// k_local.hip -- a call's compressed keys in[n] decoded into loc[n] in the registry's form, an
+// invalid key all-zero, with gbls_g1_decompress(validate = 1)'s statuses
+void launch_g1_local_decode(hipStream_t st, const uint8_t *in, uint32_t n, g1a *loc, int32_t *status);
 void launch_sk_to_pk(hipStream_t st, const uint8_t *sks, uint32_t n, g1a *out);
 void launch_sign(hipStream_t st, const uint8_t *sks, const g2a *H, uint32_t n, g2a *out);
 void launch_mad_peak(hipStream_t st, unsigned blocks, uint64_t *sink, uint32_t iters, uint32_t seed);

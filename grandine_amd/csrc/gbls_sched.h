@@ -136,7 +136,34 @@ struct KeySource {
   const void *span_pieces = nullptr;
   const void *span_sets = nullptr;
   uint32_t span_np = 0, span_max_pieces = 0;
+  // local key sets (with the span fields; gbls_local.h): `local` marks a source of the local calls,
+  // pkb[npkb] its call-local table of compressed keys; a set with com[i] == kLocalKeys sums the
+  // table positions of its off range.  Device source: the compressed bytes (loc_in), the decoded
+  // table loc[npkb] with its statuses (loc_st), and the local sets' pieces, the tail
+  // [span_np - loc_np, span_np) of the piece array, with their longest list.
+  bool local = false;
+  const uint8_t (*pkb)[48] = nullptr;
+  size_t npkb = 0;
+  const uint8_t *loc_in = nullptr;
+  const G1 *loc = nullptr;
+  int32_t *loc_st = nullptr;
+  uint32_t loc_np = 0, loc_max_len = 0;
 };
+
+// Merging callers of the local calls: the positions of a caller's LOCAL sets (com[i] ==
+// kLocalSet, gbls_local.h kLocalKeys) move up by the number of local keys of the callers before
+// it; registry indices stay as they are.  idx: the merged index array, off/com: the merged
+// offsets and slots, [at, at + n) this caller's sets.  A position past the caller's OWN table
+// must stay rejected after the move, so it is sent to the merged table's end (total), never
+// into a later caller's keys.
+constexpr uint32_t kLocalSet = 0xfffffffeu;
+inline void local_rebase(uint32_t *idx, const uint32_t *off, const uint32_t *com, size_t at, size_t n, uint32_t before,
+                         uint32_t own, uint32_t total) {
+  for (size_t i = at; i < at + n; i++) {
+    if (com[i] != kLocalSet) continue;
+    for (uint32_t k = off[i]; k < off[i + 1]; k++) idx[k] = idx[k] < own ? idx[k] + before : total;
+  }
+}
 
 // One caller's batch (host pointers, borrowed for the call).  rands == nullptr: independent
 // single checks (Signature::verify / fast_aggregate_verify semantics: r_i = 1, the
@@ -156,15 +183,17 @@ struct Request {
   const uint8_t *sigs_c = nullptr;  // compressed signatures instead of sigs (96 B each)
   int32_t *sig_status = nullptr;    // their decompression statuses (with sigs_c)
   int32_t *key_status = nullptr;    // the sets' key statuses (a span source only)
+  int32_t *pkb_status = nullptr;    // the local keys' statuses (a local source only, optional)
   int prio = 0;                     // 1: block import
   bool done = false, ok = false;
   int err = 0;                      // the verifier's side-channel error code
   bool spans() const { return src.cbits != nullptr; }
   // A span source (com, cbits, bits, bits_off; idx and off for its plain sets, off == nullptr
-  // when it has none) is a kind of its own whether or not it carries index ranges.
+  // when it has none) is a kind of its own whether or not it carries index ranges; a local
+  // source (span | local: a span source with a key table, empty or not) another.
   int kind() const {
     const int sig = (sigs_c ? 4 : 0) | (rands ? 0 : 8);
-    return spans() ? 16 | sig : (src.pts ? 1 : 0) | (src.off ? 2 : 0) | sig;
+    return spans() ? 16 | (src.local ? 32 : 0) | sig : (src.pts ? 1 : 0) | (src.off ? 2 : 0) | sig;
   }
   size_t nkeys() const { return src.off ? src.off[n] : spans() ? 0 : n; }
 };
@@ -189,10 +218,21 @@ struct Config {
 // signature statuses (and, for span sources, key statuses) are copied back from its own range.
 // Span sources: com and cbits are concatenated, the bit strings too with bits_off rebased, the
 // plain sets' indices with off rebased (a request without off contributes empty ranges).
+// Local sources: the key tables are concatenated too, the positions of each caller's LOCAL sets
+// move up by the local keys before that caller (registry indices stay; gbls_local.h
+// local_rebase), and every caller gets its own slice of the keys' statuses.  Tables that
+// together do not fit 32 bits are not merged: each request then runs on its own.
 template <class Req, class Verify>
 void run_merged(std::vector<Req *> &batch, Verify &&verify) {
   if (batch.size() == 1) {
     verify(*batch[0]);
+    return;
+  }
+  const bool local = batch[0]->src.local;
+  uint64_t nloc = 0;
+  for (Req *r : batch) nloc += local ? r->src.npkb : 0;
+  if (nloc > 0xffffffffull) {
+    for (Req *r : batch) verify(*r);
     return;
   }
   using G1 = typename Req::g1_type;
@@ -227,8 +267,10 @@ void run_merged(std::vector<Req *> &batch, Verify &&verify) {
     bits.resize(nb);
     boff.resize(n + 1);
   }
+  std::vector<uint8_t> pkb(local ? 48 * (size_t)nloc : 0);
+  std::vector<int32_t> pst(local ? (size_t)nloc : 0, 1 /* BAD_ENCODING until decoded */);
   std::vector<int32_t> v(nseg, 5 /* VERIFY_FAIL */);
-  size_t at = 0, sat = 0, kat = 0, bat = 0;
+  size_t at = 0, sat = 0, kat = 0, bat = 0, lat = 0;
   seg[0] = 0;
   for (Req *r : batch) {
     std::memcpy(&msgs[32 * at], r->msgs, 32 * r->n);
@@ -254,6 +296,12 @@ void run_merged(std::vector<Req *> &batch, Verify &&verify) {
       for (size_t i = 0; i <= r->n; i++) boff[at + i] = (uint32_t)(bat + r->src.bits_off[i]);
       bat += nb;
     }
+    if (local) {
+      if (r->src.npkb) std::memcpy(&pkb[48 * lat], r->src.pkb, 48 * r->src.npkb);
+      if (r->src.off)
+        local_rebase(idx.data(), off.data(), com.data(), at, r->n, (uint32_t)lat, (uint32_t)r->src.npkb, (uint32_t)nloc);
+      lat += r->src.npkb;
+    }
     for (size_t s = 1; s <= r->nseg; s++) seg[sat + s] = (uint32_t)(at + r->seg_off[s]);
     at += r->n;
     sat += r->nseg;
@@ -273,6 +321,12 @@ void run_merged(std::vector<Req *> &batch, Verify &&verify) {
     m.src.bits_off = boff.data();
     m.key_status = kst.data();
   }
+  if (local) {
+    m.src.local = true;
+    m.src.pkb = reinterpret_cast<const uint8_t(*)[48]>(pkb.data());
+    m.src.npkb = (size_t)nloc;
+    m.pkb_status = pst.data();
+  }
   if (comp) {
     m.sigs_c = sigc.data();
     m.sig_status = sst.data();
@@ -281,7 +335,10 @@ void run_merged(std::vector<Req *> &batch, Verify &&verify) {
   verify(m);
   sat = 0;
   at = 0;
+  lat = 0;
   for (Req *r : batch) {
+    if (local && r->pkb_status && r->src.npkb) std::memcpy(r->pkb_status, &pst[lat], r->src.npkb * 4);
+    if (local) lat += r->src.npkb;
     std::memcpy(r->verdicts, &v[sat], r->nseg * 4);
     if (comp) std::memcpy(r->sig_status, &sst[at], r->n * 4);
     if (spans && r->key_status) std::memcpy(r->key_status, &kst[at], r->n * 4);

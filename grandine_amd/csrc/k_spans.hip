@@ -138,4 +138,34 @@ void launch_g1_span_keys(hipStream_t st, const g1a *reg, uint32_t nreg, const g1
     k_g1_span_keys<false><<<nblk(n), WG, 0, st>>>(ss, rows, cj, pflags, n, out, status);
 }
 
+// Local key sets (gbls_local.h): the head pieces [0, np - np_local) read the registry, the tail
+// reads the call's own table; a set's pieces lie wholly in one of the two, and the finish runs over
+// all sets as it does above.
+void launch_g1_span_keys_local(hipStream_t st, const g1a *reg, uint32_t nreg, const g1a *tab, uint32_t ntab,
+                               const g1a *loc, uint32_t nloc, const void *pieces, const void *sets,
+                               const uint32_t *rows, uint32_t np, uint32_t np_local, uint32_t n, uint32_t max_work,
+                               uint32_t max_work_local, uint32_t max_pieces, void *contrib, uint32_t *pflags,
+                               g1a *out, int32_t *status) {
+  if (!n) return;
+  constexpr uint32_t kRowFormMax = 1u << 28;
+  const SpanPiece *pp = static_cast<const SpanPiece *>(pieces);
+  const SpanSet *ss = static_cast<const SpanSet *>(sets);
+  g1j *cj = static_cast<g1j *>(contrib);
+  auto run = [&](const g1a *keys, uint32_t nkeys, uint32_t first, uint32_t cnt, uint32_t work) {
+    if (!cnt) return;
+    if (work >= g_committee_row_min && cnt < kRowFormMax)
+      k_g1_span_pieces<true><<<nblk(16 * (size_t)cnt), WG, 0, st>>>(keys, nkeys, tab, ntab, pp + first, ss, rows, cnt,
+                                                                   cj + first, pflags + first);
+    else
+      k_g1_span_pieces<false><<<nblk(cnt), WG, 0, st>>>(keys, nkeys, tab, ntab, pp + first, ss, rows, cnt, cj + first,
+                                                        pflags + first);
+  };
+  run(reg, nreg, 0, np - np_local, max_work);
+  run(loc, nloc, np - np_local, np_local, max_work_local);
+  if (max_pieces >= kSpanFoldRowMin && n < kRowFormMax)
+    k_g1_span_keys<true><<<nblk(16 * (size_t)n), WG, 0, st>>>(ss, rows, cj, pflags, n, out, status);
+  else
+    k_g1_span_keys<false><<<nblk(n), WG, 0, st>>>(ss, rows, cj, pflags, n, out, status);
+}
+
 }  // namespace gbls

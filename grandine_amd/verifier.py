@@ -57,6 +57,7 @@ class VerifierOption(enum.Enum):
 # of the participant list (1: whichever list is shorter; tools/bench_committees.py measures where
 # the absentee form stops winning)
 ABSENTEE_FORM_MAX_RATIO = 1
+G_LOCAL_KEYS = 0xFFFFFFFE  # GBLS_LOCAL_KEYS (grandine_amd/_lib.LOCAL_KEYS): the base slot of a local key set
 
 
 class Triple:
@@ -65,7 +66,7 @@ class Triple:
 
     IS_NULL = False
     __slots__ = ("message", "signature_bytes", "_key", "deferred", "indices", "slot", "committee", "absent", "bits",
-                 "span_base", "span_cbits", "span_committees")
+                 "span_base", "span_cbits", "span_committees", "key_bytes")
 
     def __init__(self, message: bytes = bytes(32), signature_bytes: bytes = None,
                  public_key: "bls.PublicKey" = None):
@@ -81,6 +82,30 @@ class Triple:
         self.span_base = None  # verify_aggregate_committees: the base slot, with
         self.span_cbits = None  # ... committee_bits as its 8 SSZ bytes (bits then spans the named committees)
         self.span_committees = None  # ... and the named committees' member indices, ascending
+        self.key_bytes = None  # verify_singular_bytes: the key as its 48 compressed bytes, not decoded on the host
+
+    def verify_singular_bytes(self, message, signature_bytes, pubkey_bytes, signature_kind=None):
+        """verify_singular for a key the caller holds only as 48 compressed bytes, with no registry
+        entry (a deposit's pubkey, a BLS-to-execution change's from_bls_pubkey, a validator above
+        the mirrored registry length): the bytes are KEPT and no host decode is performed.
+        MultiVerifier sends them as a local key set (bls.Signature.verify_items_local), decoded on
+        the device inside the submission that verifies the triple; on every other path the key is
+        decoded through the engine when it is first asked for (public_key, keys)."""
+        pubkey_bytes = bytes(pubkey_bytes)
+        if len(pubkey_bytes) != 48:
+            raise ValueError("a compressed public key is 48 bytes")
+        self.message = bytes(message)
+        self.signature_bytes = bls.SignatureBytes(bytes(signature_bytes))
+        self._key = None
+        self.deferred = self.indices = None
+        self.slot = self.committee = self.absent = self.bits = None
+        self.span_base = self.span_cbits = self.span_committees = None
+        self.key_bytes = pubkey_bytes
+
+    def _resolved(self):
+        if self._key is None:  # kept bytes: one engine decode (PublicKey::try_from), raises as it does
+            self._key = bls.PublicKey.try_from(self.key_bytes)
+        return self._key
 
     def verify_aggregate(self, message, signature_bytes, public_keys, signature_kind=None):
         """verifier.rs:387-405 without the reduce: the keys are kept and summed on the device by
@@ -95,6 +120,7 @@ class Triple:
         self.indices = None
         self.slot = self.committee = self.absent = self.bits = None
         self.span_base = self.span_cbits = self.span_committees = None
+        self.key_bytes = None
 
     def verify_aggregate_indexed(self, message, signature_bytes, validator_indices, public_keys,
                                  signature_kind=None):
@@ -189,14 +215,14 @@ class Triple:
         """The set's key: the reference's reduce(AggregatePublicKey::default, aggregate) over a
         deferred list (one engine sum), or the resolved key."""
         if self.deferred is None:
-            return self._key
+            return self._resolved()
         if not self.deferred:
             return bls.PublicKey.default()  # identity of the reduce
         return bls.PublicKey.aggregate_nonempty(self.deferred)
 
     def keys(self):
         """The engine's key operand: the deferred list, or [the key]."""
-        return list(self.deferred) if self.deferred is not None else [self._key]
+        return list(self.deferred) if self.deferred is not None else [self._resolved()]
 
 
 class Verifier:
@@ -282,8 +308,9 @@ class MultiVerifier(Verifier):
     def __init__(self, options: Iterable[VerifierOption] = (), triples: Optional[List[Triple]] = None):
         self.triples: List[Triple] = list(triples or [])
         self.options = set(options)
-        self.last_path = None  # "spans", "bits", "committees", "indices" or "points": the key form of the last finish (tests)
-        self.last_each_path = None  # "spans" or "points": the key form of the last verify_each / verify_items
+        # "local", "spans", "bits", "committees", "indices" or "points": the key form of the last finish (tests)
+        self.last_path = None
+        self.last_each_path = None  # "local", "spans" or "points": the key form of the last verify_each / verify_items
         self.last_each_status = None  # verify_each on "spans": per set (signature status, key status)
 
     @classmethod
@@ -293,6 +320,11 @@ class MultiVerifier(Verifier):
     def verify_singular(self, message, signature_bytes, cached_public_key, signature_kind):
         public_key = cached_public_key.decompress()
         self.triples.append(Triple(message, signature_bytes, public_key))
+
+    def verify_singular_bytes(self, message, signature_bytes, pubkey_bytes, signature_kind=None):
+        t = Triple()
+        t.verify_singular_bytes(message, signature_bytes, pubkey_bytes, signature_kind)
+        self.triples.append(t)
 
     def verify_aggregate(self, message, signature_bytes, public_keys, signature_kind):
         t = Triple()
@@ -326,6 +358,8 @@ class MultiVerifier(Verifier):
         do not qualify: at least one triple came through verify_aggregate_committees, every slot it
         names keeps exactly the members the triple was built from, and the other triples qualify as
         for "bits" (a single-committee triple is then a span with one bit)."""
+        if any(t.key_bytes is not None for t in self.triples):
+            return None  # (kept key bytes: _local_sets)
         spans = [t for t in self.triples if t.span_base is not None]
         if not spans:
             return None
@@ -353,6 +387,48 @@ class MultiVerifier(Verifier):
                 base.append(None), cbits.append(bytes(8)), fields.append(b""), lists.append(t.indices)
         return base, cbits, fields, lists
 
+    def _local_sets(self):
+        """The triples as span, plain and LOCAL sets plus the call's key table, or None: at least one
+        triple keeps its key bytes (verify_singular_bytes) and the others qualify for "spans".  A
+        key that several triples name is in the table once."""
+        local = [t for t in self.triples if t.key_bytes is not None]
+        if not local:
+            return None
+        rest = MultiVerifier(triples=[t for t in self.triples if t.key_bytes is None])._span_sets()
+        if rest is None:
+            return None
+        table, at = [], {}
+        rest = iter(zip(*rest))
+        base, cbits, fields, lists = [], [], [], []
+        for t in self.triples:
+            if t.key_bytes is None:
+                b, c, f, l = next(rest)
+            else:
+                if t.key_bytes not in at:
+                    at[t.key_bytes] = len(table)
+                    table.append(t.key_bytes)
+                b, c, f, l = G_LOCAL_KEYS, bytes(8), b"", [at[t.key_bytes]]
+            base.append(b), cbits.append(c), fields.append(f), lists.append(l)
+        return base, cbits, fields, lists, table
+
+    def _finish_local(self, msgs, sigs, randoms, flags):
+        """The "local" path, or None when the triples do not qualify (_local_sets): the batch as ONE
+        item of verify_items_local.  Returns as multi_verify_compressed: a signature's or a local
+        key's decoding error comes first."""
+        sets = self._local_sets()
+        if sets is None:
+            return None
+        self.last_path = "local"
+        verdicts, statuses, key_statuses = bls.Signature.verify_items_local(
+            msgs, sigs, *sets, [0, len(msgs)], randoms, flags, with_statuses=True)
+        for st, _ in statuses:
+            if st != 0:
+                return st
+        for st in key_statuses:
+            if st != 0:
+                return st
+        return 0 if verdicts[0] else 5
+
     def _finish_spans(self, msgs, sigs, randoms, flags):
         """The "spans" path, or None when the triples do not qualify (_span_sets)."""
         sets = self._span_sets()
@@ -375,9 +451,11 @@ class MultiVerifier(Verifier):
         indexed = all(t.indices is not None and bls.Registry.covers(t.indices) for t in self.triples)
         com = [t for t in self.triples if t.slot is not None]
         # attestations over several committees first: base slot, committee_bits and the one bit string
-        rc = self._finish_spans(msgs, sigs, randoms, flags)
+        rc = self._finish_local(msgs, sigs, randoms, flags)
+        if rc is None:
+            rc = self._finish_spans(msgs, sigs, randoms, flags)
         if rc is not None:
-            pass  # sent: last_path == "spans"
+            pass  # sent: last_path == "local" or "spans"
         elif com and all(bls.Committees.has_members(t.slot) and bls.Committees.covers(t.slot, t.committee)
                        for t in com) and all(t.indices is not None and bls.Registry.covers(t.indices)
                                              for t in self.triples if t.slot is None):
@@ -424,6 +502,13 @@ class MultiVerifier(Verifier):
         status, key status)."""
         if not self.triples:
             return []
+        sets = self._local_sets()
+        if sets is not None:  # kept key bytes among triples that qualify for "spans": decoded on the device
+            self.last_each_path = "local"
+            outcomes, _ = bls.Signature.verify_each_local(
+                [t.message for t in self.triples], [t.signature_bytes for t in self.triples], *sets)
+            self.last_each_status = [(st, kst) for st, kst, _ in outcomes]
+            return [st == 0 and kst == 0 and ok for st, kst, ok in outcomes]
         sets = self._span_sets()
         if sets is not None:
             self.last_each_path = "spans"
@@ -452,12 +537,18 @@ class MultiVerifier(Verifier):
         offsets = [sum(1 for k in owner if k < s) for s in range(nitems + 1)]
         if not self.triples:
             return []
+        flags = 0x1 if VerifierOption.BlockImport in self.options else 0
+        sets = self._local_sets()
+        if sets is not None:
+            self.last_each_path = "local"
+            return bls.Signature.verify_items_local(
+                [t.message for t in self.triples], [t.signature_bytes for t in self.triples], *sets, offsets, randoms,
+                flags)
         sets = self._span_sets()
         if sets is None:
             each = self.verify_each()  # last_each_path == "points"
             return [offsets[s] < offsets[s + 1] and all(each[offsets[s]:offsets[s + 1]]) for s in range(nitems)]
         self.last_each_path = "spans"
-        flags = 0x1 if VerifierOption.BlockImport in self.options else 0
         return bls.Signature.verify_items_spans(
             [t.message for t in self.triples], [t.signature_bytes for t in self.triples], *sets, offsets, randoms, flags)
 

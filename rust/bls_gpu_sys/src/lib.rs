@@ -27,8 +27,10 @@ pub mod ffi;
 pub mod ffi_bits;
 pub mod ffi_committees;
 pub mod ffi_each;
+pub mod ffi_local;
 pub mod ffi_msgcache;
 pub mod ffi_spans;
+pub mod local;
 pub mod msgcache;
 pub mod spans;
 

@@ -50,10 +50,28 @@ committee absent, one signature bad, the forms alternating:
   two           gbls_g1_aggregate_spans, then gbls_verify_batch_compressed over the 192 resulting
                 points: two submissions (yardstick b)
 
+With --local the keys are local ones (include/grandine_bls_gpu_local.h: compressed keys with no
+registry entry, decoded inside the submission), three parts:
+
+  forms             gbls_g1_aggregate_local over 1, 16, 64, 256, 2048 and 8192 one-key local sets
+                    (keys_local) against gbls_g1_decompress(validate = 1) on the same bytes
+                    (decompress).  The decode kernel's form follows the table's size (kLocalWaveMax,
+                    gbls_local.h); an experiment build (make EXTRA=-DGBLS_LOCAL_WAVE_MAX=...)
+                    loaded through GBLS_LIB shows the other form at the same sizes.
+  deposits16        16 one-key local sets, one with a bad signature: gbls_verify_each_local
+                    (each_local) against gbls_g1_decompress, then gbls_verify_batch_compressed over
+                    the points (two: two submissions).
+  block8x64x512+16  the --spans block plus 16 one-key local sets: gbls_verify_items_local, one
+                    item, GBLS_CALL_BLOCK (items_local) against gbls_g1_decompress, the spans call
+                    for the block and gbls_multi_verify_compressed_ex over the 16 (three: three
+                    submissions); block is the items call of grandine_bls_gpu_each.h over the block
+                    alone, so that the 16 sets' cost shows.
+
   python tools/bench_committees.py                       # both shapes, one JSON line per point
   python tools/bench_committees.py --bits                # ... the aggregation-bit leg
   python tools/bench_committees.py --spans               # the span-set leg (its own shape)
   python tools/bench_committees.py --each                # per-set and per-item verdicts (its own shape)
+  python tools/bench_committees.py --local               # local key sets (--parts forms,deposits16,block)
   GBLS_COMMITTEE_ROW_MIN=1 python tools/bench_committees.py --tuning --keys-only
 """
 import argparse
@@ -303,6 +321,155 @@ def each_leg(a, G, F, L, emit, absent_counts):
         emit(res)
 
 
+def local_leg(a, G, F, L, emit, absent_counts):
+    """Local key sets: the decode forms, deposits16 and block8x64x512+16."""
+    ptr = lambda x: x.ctypes.data_as(ctypes.c_void_p)
+    parts = set(a.parts.split(",")) if a.parts else {"forms", "deposits16", "block"}
+
+    def report(shape, extra, call, kinds):
+        f, calls = timed(call, kinds, a.warmup, a.window, a.runs)
+        res = dict({"shape": shape, "calls_per_run": calls}, **extra)
+        for kind in kinds:
+            res[kind] = summary(f[kind])
+            res[kind]["runs_us"] = [round(x, 1) for x in f[kind]]
+        emit(res)
+
+    def local_sets(nl, first=0):
+        """nl one-key local sets behind `first` other sets: com, cbits, bits_off, pk_idx, pk_off tails."""
+        return (np.full(nl, G.LOCAL_KEYS, dtype=np.uint32), np.arange(nl, dtype=np.uint32),
+                np.arange(first, first + nl + 1, dtype=np.uint32))
+
+    lsks, lcomp = F.registry(8192, b"bench-committees/local")
+    if "forms" in parts:
+        for nk in (1, 16, 64, 256, 2048, 8192):
+            table = ctypes.create_string_buffer(lcomp[:48 * nk], 48 * nk)
+            com, idx, off = local_sets(nk)
+            masks, boff = np.zeros((nk, 8), dtype=np.uint8), np.zeros(nk + 1, dtype=np.uint32)
+            out, st, pst = ctypes.create_string_buffer(96 * nk), G.i32_array(nk), G.i32_array(nk)
+
+            def call(which):
+                t0 = time.perf_counter()
+                if which == "keys_local":
+                    rc = L.gbls_g1_aggregate_local(ptr(com), ptr(masks), None, ptr(boff), ptr(idx), ptr(off), table, nk,
+                                                   nk, out, st, pst)
+                else:
+                    rc = L.gbls_g1_decompress(table, nk, 1, out, st)
+                dt = time.perf_counter() - t0
+                if rc != G.SUCCESS or any(st[i] for i in range(nk)):
+                    raise SystemExit("forms %d %s: rc=%d err=%d" % (nk, which, rc, L.gbls_last_error()))
+                return dt
+
+            report("local_forms", {"keys": nk}, call, ["keys_local", "decompress"])
+    if "deposits16" in parts:
+        nl = 16
+        table = ctypes.create_string_buffer(lcomp[:48 * nl], 48 * nl)
+        msgs = F.messages(nl, b"bench-committees/deposits16")
+        sigs = bytearray(F.sign(lsks[:nl], msgs))
+        sigs[192 * 5:192 * 6] = sigs[192 * 6:192 * 7]  # one deposit with another's signature
+        sig_c = ctypes.create_string_buffer(96 * nl)
+        G.check(L.gbls_g2_compress(bytes(sigs), nl, sig_c), "gbls_g2_compress")
+        com, idx, off = local_sets(nl)
+        masks, boff = np.zeros((nl, 8), dtype=np.uint8), np.zeros(nl + 1, dtype=np.uint32)
+        pts, st, kst, v, pst = ctypes.create_string_buffer(96 * nl), G.i32_array(nl), G.i32_array(nl), G.i32_array(nl), G.i32_array(nl)
+
+        def call(which):
+            t0 = time.perf_counter()
+            if which == "each_local":
+                rc = L.gbls_verify_each_local(msgs, sig_c, ptr(com), ptr(masks), None, ptr(boff), ptr(idx), ptr(off), table,
+                                              nl, nl, st, kst, v, pst)
+            else:
+                rc = L.gbls_g1_decompress(table, nl, 1, pts, pst)
+                if rc == G.SUCCESS:
+                    rc = L.gbls_verify_batch_compressed(msgs, sig_c, pts, ptr(off), nl, st, v)
+            dt = time.perf_counter() - t0
+            if rc != G.SUCCESS or [i for i in range(nl) if v[i] != G.SUCCESS] != [5]:
+                raise SystemExit("deposits16 %s: rc=%d err=%d" % (which, rc, L.gbls_last_error()))
+            return dt
+
+        report("deposits16", {"sets": nl}, call, ["each_local", "two"])
+    if "block" not in parts:
+        return
+    # the --spans block (8 span sets over 64 committees of 512, 4 plain sets) plus 16 local sets
+    nset, per_set, size, nplain, nl = 8, 64, 512, 4, 16
+    ncom, nb = nset * per_set, nset + nplain
+    n, nreg = nb + nl, ncom * size
+    seed = b"bench-committees/block8x64x512"
+    sks, comp = F.registry(nreg, seed)
+    if F.load_registry(comp).any():
+        raise SystemExit("registry load failed")
+    perm, coff = F.committees(nreg, ncom, 7)
+    perm_c, coff_c = np.ascontiguousarray(perm, dtype=np.uint32), np.ascontiguousarray(coff, dtype=np.uint32)
+    cst = G.i32_array(ncom)
+    rc = L.gbls_committees_set_members(0, ptr(perm_c), ptr(coff_c), ncom, cst)
+    if rc != G.SUCCESS or any(cst[c] for c in range(ncom)):
+        raise SystemExit("gbls_committees_set_members rc=%d" % rc)
+    sk = np.array(sks, dtype=object)
+    totals = [int(sum(sk[perm[coff[c]:coff[c + 1]]])) for c in range(ncom)]
+    plain = [int(perm[coff[7 * i + 3]]) for i in range(nplain)]
+    msgs = F.messages(n, seed + b"+16")
+    rands = (ctypes.c_uint64 * n)(*F.rands(n, n + size))
+    table = ctypes.create_string_buffer(lcomp[:48 * nl], 48 * nl)
+    for k in absent_counts:
+        sums = []
+        for i in range(nset):
+            t = 0
+            for c in range(per_set * i, per_set * (i + 1)):
+                t += totals[c] - int(sum(sk[perm[coff[c]:coff[c] + k]]))
+            sums.append(t % F.R_ORDER)
+        sums += [sks[v] for v in plain] + lsks[:nl]
+        sig_c = ctypes.create_string_buffer(96 * n)
+        G.check(L.gbls_g2_compress(F.sign(sums, msgs), n, sig_c), "gbls_g2_compress")
+        lcom, lidx, _ = local_sets(nl)
+        base = np.concatenate([np.array([per_set * i for i in range(nset)] + [G.NO_COMMITTEE] * nplain, dtype=np.uint32), lcom])
+        masks = np.zeros((n, 8), dtype=np.uint8)
+        masks[:nset] = np.uint8(0xFF)
+        fields = []
+        for i in range(nset):
+            bits = np.zeros(8 * (per_set * size // 8 + 1), dtype=np.uint8)
+            for c in range(per_set):
+                bits[c * size + k:(c + 1) * size] = 1
+            bits[per_set * size] = 1  # the delimiter
+            fields.append(np.packbits(bits, bitorder="little").tobytes())
+        s_all = ctypes.create_string_buffer(b"".join(fields), sum(len(x) for x in fields))
+        s_off = np.zeros(n + 1, dtype=np.uint32)
+        s_off[1:nset + 1] = np.cumsum([len(x) for x in fields])
+        s_off[nset + 1:] = s_off[nset]
+        q_idx = np.concatenate([np.array(plain, dtype=np.uint32), lidx])
+        q_off = np.zeros(n + 1, dtype=np.uint32)
+        q_off[nset + 1:] = np.arange(1, nplain + nl + 1)
+        seg_all, seg_block = np.array([0, n], dtype=np.uint32), np.array([0, nb], dtype=np.uint32)
+        l_off = np.arange(nl + 1, dtype=np.uint32)
+        l_msgs = ctypes.create_string_buffer(msgs[32 * nb:], 32 * nl)
+        l_sig = ctypes.create_string_buffer(sig_c.raw[96 * nb:], 96 * nl)
+        l_rands = (ctypes.c_uint64 * nl)(*[rands[nb + i] for i in range(nl)])
+        pts, st, kst, v, pst = ctypes.create_string_buffer(96 * nl), G.i32_array(n), G.i32_array(n), G.i32_array(1), G.i32_array(nl)
+
+        def call(which):
+            t0 = time.perf_counter()
+            if which == "items_local":
+                rc = L.gbls_verify_items_local(msgs, sig_c, ptr(base), ptr(masks), s_all, ptr(s_off), ptr(q_idx), ptr(q_off),
+                                               table, nl, rands, n, ptr(seg_all), 1, st, kst, v, pst, G.CALL_BLOCK)
+                rc = rc or v[0]
+            elif which == "block":
+                rc = L.gbls_verify_items_spans(msgs, sig_c, ptr(base), ptr(masks), s_all, ptr(s_off), ptr(q_idx), ptr(q_off),
+                                               rands, nb, ptr(seg_block), 1, st, kst, v, G.CALL_BLOCK)
+                rc = rc or v[0]
+            else:
+                rc = L.gbls_g1_decompress(table, nl, 1, pts, pst)
+                if rc == G.SUCCESS:
+                    rc = L.gbls_multi_verify_spans(msgs, sig_c, ptr(base), ptr(masks), s_all, ptr(s_off), ptr(q_idx),
+                                                   ptr(q_off), rands, nb, st, G.CALL_BLOCK)
+                if rc == G.SUCCESS:
+                    rc = L.gbls_multi_verify_compressed_ex(l_msgs, l_sig, pts, None, ptr(l_off), l_rands, nl, st,
+                                                           G.CALL_BLOCK)
+            dt = time.perf_counter() - t0
+            if rc != G.SUCCESS:
+                raise SystemExit("block8x64x512+16 absent=%d %s: rc=%d err=%d" % (k, which, rc, L.gbls_last_error()))
+            return dt
+
+        report("block8x64x512+16", {"sets": n, "local_sets": nl, "absent": k}, call, ["items_local", "three", "block"])
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--runs", type=int, default=5)
@@ -319,6 +486,9 @@ def main():
     ap.add_argument("--each", action="store_true",
                     help="the per-set / per-item leg: gossip64x3 through the each and items calls and the two forms "
                          "without them")
+    ap.add_argument("--local", action="store_true",
+                    help="the local key set leg: the decode forms, deposits16 and block8x64x512+16")
+    ap.add_argument("--parts", default="", help="with --local: comma-separated parts (forms, deposits16, block)")
     ap.add_argument("--out", default="", help="also append the JSON lines to this file")
     ap.add_argument("--tuning", action="store_true", help="let the engine read its GBLS_* tuning variables")
     a = ap.parse_args()
@@ -341,8 +511,10 @@ def main():
         spans_leg(a, G, F, L, emit, [int(x) for x in a.absent.split(",")] if a.absent else [0, 5, 51, 256])
     if a.each:
         each_leg(a, G, F, L, emit, [int(x) for x in a.absent.split(",")] if a.absent else [0, 5, 51])
+    if a.local:
+        local_leg(a, G, F, L, emit, [int(x) for x in a.absent.split(",")] if a.absent else [5])
     for name, ncom, size in SHAPES:
-        if a.spans or a.each or (want and name not in want):
+        if a.spans or a.each or a.local or (want and name not in want):
             continue
         nreg = ncom * size
         seed = b"bench-committees/" + name.encode()
