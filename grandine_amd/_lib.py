@@ -141,6 +141,14 @@ EXPORTS_MSGCACHE = [
     "gbls_msgcache_clear",
     "gbls_msgcache_stats",
 ]
+# include/grandine_bls_gpu_msgcache_checks.h (per-check calls served, prefetch)
+EXPORTS_MSGCACHE_CHECKS = [
+    "gbls_msgcache_prefetch",
+    "gbls_msgcache_serve_checks",
+    "gbls_msgcache_checks_stats",
+]
+MSGCACHE_CHECKS_STATS = ("prefetched", "check_lookups", "check_hits", "check_published")
+PREFETCH_ENTERED, PREFETCH_PRESENT, PREFETCH_SKIPPED = 0, 1, 2
 MSGCACHE_STATS = ("lookups", "hits", "misses", "published", "evictions", "bypassed", "entries", "reserved")
 
 
@@ -254,13 +262,16 @@ def load_library():
                 "gbls_msgcache_slots": (_sz, []),
                 "gbls_msgcache_clear": (_c.c_int, []),
                 "gbls_msgcache_stats": (_c.c_int, [_vp]),
+                "gbls_msgcache_prefetch": (_c.c_int, [_vp, _sz, _vp]),
+                "gbls_msgcache_serve_checks": (_c.c_int, [_c.c_int]),
+                "gbls_msgcache_checks_stats": (_c.c_int, [_vp]),
             }
             for name, (res, args) in sig.items():
-                # an experiment build (GBLS_LIB) may predate the message line cache, the bits, the
-                # spans, the each or the local calls: A/B tools load it and leave those entries
-                # alone; the package's own library must have them
-                if (_override and name in EXPORTS_MSGCACHE + EXPORTS_BITS + EXPORTS_SPANS + EXPORTS_EACH
-                        + EXPORTS_LOCAL and not hasattr(lib, name)):
+                # an experiment build (GBLS_LIB) may predate the message line cache (or its
+                # per-check extension), the bits, the spans, the each or the local calls: A/B tools
+                # load it and leave those entries alone; the package's own library must have them
+                if (_override and name in EXPORTS_MSGCACHE + EXPORTS_MSGCACHE_CHECKS + EXPORTS_BITS + EXPORTS_SPANS
+                        + EXPORTS_EACH + EXPORTS_LOCAL and not hasattr(lib, name)):
                     continue
                 fn = getattr(lib, name)
                 fn.restype = res

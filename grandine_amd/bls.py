@@ -773,6 +773,39 @@ class MessageCache:
         return {name: int(out[i]) for i, name in enumerate(G.MSGCACHE_STATS) if name != "reserved"}
 
     @classmethod
+    def prefetch(cls, messages) -> list:
+        """gbls_msgcache_prefetch: enters the 32-byte ``messages`` (signing roots the node derived
+        itself -- the caller vouches for them) on every engine device, without any signature.
+        Returns one status per message: ``G.PREFETCH_ENTERED``, ``PREFETCH_PRESENT`` or
+        ``PREFETCH_SKIPPED`` (cache off, or no slot to spare).  Needs the engine unless the cache is
+        off."""
+        messages = [bytes(m) for m in messages]
+        if any(len(m) != 32 for m in messages):
+            raise ValueError("prefetch takes 32-byte messages")
+        n = len(messages)
+        status = G.i32_array(n)
+        L = G.load_library()
+        rc = L.gbls_msgcache_prefetch(G.buf(b"".join(messages)), n, status)
+        if rc != G.SUCCESS:
+            raise G.EngineUnavailable("gbls_msgcache_prefetch failed: rc=%d err=%d" % (rc, L.gbls_last_error()))
+        return [int(status[i]) for i in range(n)]
+
+    @classmethod
+    def serve_checks(cls, on: bool) -> bool:
+        """gbls_msgcache_serve_checks: per-check calls (verify, fast_aggregate_verify, the
+        ``*_verify_batch`` calls, verify_each_*) are planned by message and served by the cache
+        while on.  Off by default, process-wide and sticky.  Returns the previous setting."""
+        return bool(G.load_library().gbls_msgcache_serve_checks(1 if on else 0))
+
+    @classmethod
+    def checks_stats(cls) -> dict:
+        """gbls_msgcache_checks_stats as a dict: prefetched, check_lookups, check_hits,
+        check_published (counters since the process started)."""
+        out = (ctypes.c_uint64 * 4)()
+        G.check(G.load_library().gbls_msgcache_checks_stats(out), "gbls_msgcache_checks_stats")
+        return {name: int(out[i]) for i, name in enumerate(G.MSGCACHE_CHECKS_STATS)}
+
+    @classmethod
     def memory_bytes(cls, slots: int) -> int:
         """Device memory per engine device at this capacity, spare slots included."""
         slots = int(slots)

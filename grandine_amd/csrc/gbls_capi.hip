@@ -36,6 +36,7 @@
 #include "../../include/grandine_bls_gpu.h"
 #include "../../include/grandine_bls_gpu_committees.h"
 #include "../../include/grandine_bls_gpu_msgcache.h"
+#include "../../include/grandine_bls_gpu_msgcache_checks.h"
 #include "../../include/grandine_bls_gpu_bits.h"
 #include "../../include/grandine_bls_gpu_each.h"
 #include "../../include/grandine_bls_gpu_spans.h"
@@ -46,6 +47,7 @@
 #include "gbls_dedup.h"
 #include "gbls_members.h"
 #include "gbls_msgcache.h"
+#include "gbls_msgcache_checks.h"
 #include "gbls_sched.h"
 #include "gbls_spans.h"
 #include "gbls_local.h"
@@ -274,6 +276,7 @@ struct Ctx {
   // until mc_finish, after the call's host synchronisation
   const msgcache::ShardPlan *mc = nullptr;
   msgcache::ShardPlan mc_plan;
+  bool mc_checks = false;  // mc_plan is a per-check plan (gbls_msgcache_checks.h): counted as such
   std::shared_ptr<struct McTable> mc_tab;
   hipEvent_t ev_lines = nullptr, ev_store = nullptr;
   // Pinned staging for host tables and host inputs: a ring of kStageRing buffers, one per call,
@@ -523,6 +526,10 @@ struct MsgCache {
   size_t slots = 0;
   uint64_t gen = 1;             // gbls_msgcache_configure starts a new one: fresh tables
   uint64_t st[msgcache::kStats] = {0};
+  // grandine_bls_gpu_msgcache_checks.h: per-check calls are planned by message and served
+  // (process-wide, sticky), and its counters (prefetched, check_lookups, check_hits, check_published)
+  std::atomic<bool> serve_checks{false};
+  uint64_t cst[4] = {0};
 } mcache;
 
 struct Device {
@@ -919,6 +926,28 @@ bool lines_unsliced(size_t nq, size_t n, const uint32_t *seg_off, size_t nseg) {
   return (nq + nseg * X) * 72 * 4 * ML_EVENTS <= g.line_budget;
 }
 
+// The set side of the main chain, shared by the pipeline's miss prefix and gbls_msgcache_prefetch (an
+// entry's lines do not depend on who made them): hash_to_G2 of nm messages up to the cofactor
+// clearing, then clearing and the lines of pairs [0, nm).  jac: H(m) stays Jacobian (over Q[2 i])
+// and its lines take it projectively (latency regime, nm <= kW4Max); ec: events per slice.
+void set_side_hash(Ctx &c, hipStream_t st, const uint8_t *msgs, const uint32_t *msg_off, uint32_t nm) {
+  {
+    StageTimer t(S_H2C_FIELD, st);
+    launch_h2c_field(st, msgs, msg_off, nm, nullptr, 0, c.U.as<fp2>());
+  }
+  StageTimer t(S_H2C_MAP, st);
+  launch_h2c_map(st, c.U.as<fp2>(), 2 * nm, c.Q.as<g2j>());
+}
+void set_side_lines(Ctx &c, hipStream_t st, uint32_t nm, bool jac, LineCols lc, int ec) {
+  {
+    StageTimer t(S_H2C_CLEAR, st);
+    if (!jac || !launch_h2c_clear_jac(st, c.Q.as<g2j>(), nm)) launch_h2c_clear(st, c.Q.as<g2j>(), nm, c.H.as<g2a>());
+  }
+  StageTimer t(S_LINES, st);
+  if (!jac || !launch_lines_jac(st, c.Q.as<g2j>(), 2, 0, nm, lc, c.lines.as<uint32_t>()))
+    launch_lines(st, c.H.as<g2a>(), 0, nm, lc, 0, ec, c.Ts.as<g2h>(), c.lines.as<uint32_t>());
+}
+
 // ----- the verification pipeline on device pointers.
 // Sets [0, n) grouped in segments by seg_off (HOST array, nseg + 1 entries); per segment
 // a Miller partial (no final exponentiation) and an error flag.  rands == nullptr
@@ -961,12 +990,14 @@ bool pipeline_partials(Ctx &c, Device &d, const uint8_t *msgs, const uint32_t *m
   }
   const dedup::Plan *pl = c.plan;
   c.plan = nullptr;
-  if (pl && (!rands || pl->n != n || pl->nseg != nseg)) return fail(GBLS_ERR_ARG);
+  if (pl && (pl->n != n || pl->nseg != nseg)) return fail(GBLS_ERR_ARG);
   // message line cache: the groups that missed are pairs [0, nm), hashed and given lines as ever;
   // the groups that hit are pairs [nm, nq), their lines copied from the cache table
   const msgcache::ShardPlan *mcp = c.mc;
   c.mc = nullptr;
   if (mcp && (!pl || pl != &mcp->groups || !c.mc_tab || !c.mc_tab->dev)) return fail(GBLS_ERR_ARG);
+  // without random scalars (r_i = 1) only a per-check plan of the line cache: one pair per check
+  if (pl && !rands && (!mcp || pl->ngroups != n || nseg != n || grp > 1)) return fail(GBLS_ERR_ARG);
   const uint32_t *pair_of = mcp ? mcp->pair_of.data() : nullptr;  // group -> pair
   const size_t nq = pl ? pl->ngroups : n;  // set-side Miller pairs (= messages hashed without the cache)
   const size_t nm = mcp ? mcp->M : nq;     // messages hashed, pairs whose lines are generated
@@ -1084,6 +1115,9 @@ bool pipeline_partials(Ctx &c, Device &d, const uint8_t *msgs, const uint32_t *m
   if (!c.upload_staged(c.tab, tab.data(), tab.size() * 4, st)) return false;
   const uint32_t N = (uint32_t)n, NP = (uint32_t)np, NS = (uint32_t)nseg, NQ = (uint32_t)nq, NM = (uint32_t)nm;
   const uint32_t n_store = mcp ? (uint32_t)mcp->store_pair.size() : 0;
+  // a per-check plan's pairs that wait for a store of this very call (the other checks of a message
+  // that missed): loaded on the main stream behind it
+  const uint32_t n_copy = mcp ? mcp->ncopy : 0;
   const bool hash_msgs = !mcp || NM;  // a call whose messages all hit has no hash_to_G2 and no set-side lines
   if (pl && trace_dedup())
     fprintf(stderr, "gbls dedup: sets=%zu segments=%zu groups=%zu pairs=%zu%s\n", n, nseg, nq, np,
@@ -1106,18 +1140,11 @@ bool pipeline_partials(Ctx &c, Device &d, const uint8_t *msgs, const uint32_t *m
   HIPCHK(hipStreamWaitEvent(side1, c.ev_fork, 0));
   HIPCHK(hipStreamWaitEvent(side2, c.ev_fork, 0));
   // main stream first: its first kernels reach the GPU before the side streams' floods
-  if (mcp && NQ > NM) {  // the hits' lines, from the cache table into their columns
+  if (mcp && NQ - n_copy > NM) {  // the hits' lines, from the cache table into their columns
     StageTimer t(S_LC_LOAD, st);
-    launch_linecache_load(st, c.mc_tab->dev, T + mc_ix_at, NM, NQ - NM, lc, c.lines.as<uint32_t>());
+    launch_linecache_load(st, c.mc_tab->dev, T + mc_ix_at, NM, NQ - n_copy - NM, lc, c.lines.as<uint32_t>());
   }
-  if (hash_msgs) {
-    StageTimer t(S_H2C_FIELD, st);
-    launch_h2c_field(st, msgs, msg_off, NM, nullptr, 0, c.U.as<fp2>());
-  }
-  if (hash_msgs) {
-    StageTimer t(S_H2C_MAP, st);
-    launch_h2c_map(st, c.U.as<fp2>(), 2 * NM, c.Q.as<g2j>());
-  }
+  if (hash_msgs) set_side_hash(c, st, msgs, msg_off, NM);
   const g1a *pks = nullptr;
   const int32_t *pre = nullptr;
   if (!resolve_pks(c, d, src, n, side1, &pks, &pre)) return false;
@@ -1182,19 +1209,23 @@ bool pipeline_partials(Ctx &c, Device &d, const uint8_t *msgs, const uint32_t *m
   // latency regime: H(m) stays Jacobian (over Q[2 i]) and its lines take it projectively,
   // no inversion on the main chain
   const bool jac_h = !sliced && NM <= kW4Max;
-  if (hash_msgs) {
-    StageTimer t(S_H2C_CLEAR, st);
-    if (!jac_h || !launch_h2c_clear_jac(st, c.Q.as<g2j>(), NM))
-      launch_h2c_clear(st, c.Q.as<g2j>(), NM, c.H.as<g2a>());
-  }
-  if (hash_msgs) {  // the sets' lines of the first event slice, before the join
-    StageTimer t(S_LINES, st);
-    if (!jac_h || !launch_lines_jac(st, c.Q.as<g2j>(), 2, 0, NM, lc, c.lines.as<uint32_t>()))
-      launch_lines(st, c.H.as<g2a>(), 0, NM, lc, 0, EC, c.Ts.as<g2h>(), c.lines.as<uint32_t>());
-  }
+  // the sets' lines of the first event slice, before the join
+  if (hash_msgs) set_side_lines(c, st, NM, jac_h, lc, EC);
   HIPCHK(hipEventRecord(c.ev_side1, side1));
   HIPCHK(hipEventRecord(c.ev_side2, side2));
-  if (n_store) {
+  if (n_store && n_copy) {
+    // Per-check plan with a missed message that several checks carry: its first pair's lines go to
+    // the slot and from there to the other pairs' columns, both on the main stream, ahead of the
+    // Miller product that reads them.
+    const uint32_t *ix = T + mc_ix_at + (NQ - NM);
+    {
+      StageTimer t(S_LC_STORE, st);
+      launch_linecache_store(st, c.mc_tab->dev, ix, ix + n_store, n_store, lc, c.lines.as<uint32_t>());
+    }
+    StageTimer t(S_LC_LOAD, st);
+    launch_linecache_load(st, c.mc_tab->dev, T + mc_ix_at + (NQ - NM - n_copy), NQ - n_copy, n_copy, lc,
+                          c.lines.as<uint32_t>());
+  } else if (n_store) {
     // The misses' lines go to their cache slots on side stream 1, which is idle from here on:
     // behind the lines (ev_lines), beside the Miller product, off the path to the verdict.  The
     // main stream waits for the copy only at its very end, so that the call's completion (the
@@ -1238,7 +1269,7 @@ bool pipeline_partials(Ctx &c, Device &d, const uint8_t *msgs, const uint32_t *m
                     T + mt.grp_off, (uint32_t)mt.ngroup, e0, e1, c.V0.as<fp12>(), c.V28.as<uint32_t>(), pcn);
   }
   ml_tail(c, st, mt, T, (uint32_t)nms, partials, n <= kSplitHornerMaxSets);
-  if (n_store) HIPCHK(hipStreamWaitEvent(st, c.ev_store, 0));
+  if (n_store && !n_copy) HIPCHK(hipStreamWaitEvent(st, c.ev_store, 0));
   if (st != caller) {
     HIPCHK(hipEventRecord(c.ev_out, st));
     HIPCHK(hipStreamWaitEvent(caller, c.ev_out, 0));
@@ -1565,6 +1596,25 @@ bool upload_pks(Ctx &c, const PkSource &host, size_t b, size_t e, hipStream_t st
 // with its device memory, at the first call after a configure) and number the pairs.  *cached:
 // the pipeline runs on the plan.  A sliced submission, or a cache switched off meanwhile, is not
 // served (the former counts its sets as bypassed).
+// d's table of the current configuration, created with its device memory at the first call after a
+// configure (under mcache.mu, the device current; *old: a replaced table, released outside the lock)
+bool mc_table(Device &d, std::shared_ptr<McTable> *old) {
+  if (d.mc_tab && d.mc_tab->gen == mcache.gen) return true;
+  *old = std::move(d.mc_tab);
+  std::shared_ptr<McTable> t = std::make_shared<McTable>();
+  const uint32_t spare = msgcache::spare_for(mcache.slots);
+  t->hipdev = d.hipdev;
+  t->gen = mcache.gen;
+  if (hipMalloc(reinterpret_cast<void **>(&t->dev), (mcache.slots + spare) * msgcache::kSlotWords * 4) !=
+      hipSuccess) {
+    t->dev = nullptr;
+    (void)hipGetLastError();
+    return fail(GBLS_ERR_HIP);
+  }
+  t->ix.reset((uint32_t)mcache.slots, spare, mcache.st);
+  d.mc_tab = std::move(t);
+  return true;
+}
 bool mc_plan_shard(Ctx &c, Device &d, bool unsliced, size_t n, bool *cached) {
   *cached = false;
   std::shared_ptr<McTable> old;  // a replaced table is released outside the lock
@@ -1574,23 +1624,15 @@ bool mc_plan_shard(Ctx &c, Device &d, bool unsliced, size_t n, bool *cached) {
     mcache.st[msgcache::BYPASSED] += n;
     return true;
   }
-  if (!d.mc_tab || d.mc_tab->gen != mcache.gen) {
-    old = std::move(d.mc_tab);
-    std::shared_ptr<McTable> t = std::make_shared<McTable>();
-    const uint32_t spare = msgcache::spare_for(mcache.slots);
-    t->hipdev = d.hipdev;
-    t->gen = mcache.gen;
-    if (hipMalloc(reinterpret_cast<void **>(&t->dev), (mcache.slots + spare) * msgcache::kSlotWords * 4) !=
-        hipSuccess) {
-      t->dev = nullptr;
-      (void)hipGetLastError();
-      return fail(GBLS_ERR_HIP);
-    }
-    t->ix.reset((uint32_t)mcache.slots, spare, mcache.st);
-    d.mc_tab = std::move(t);
-  }
+  if (!mc_table(d, &old)) return false;
   c.mc_tab = d.mc_tab;
-  msgcache::plan_cache(c.mc_plan, &c.mc_tab->ix);
+  if (c.mc_checks) {
+    msgcache::plan_checks(c.mc_plan, &c.mc_tab->ix);
+    mcache.cst[1] += c.mc_plan.D;
+    mcache.cst[2] += c.mc_plan.txn.hit.size();
+  } else {
+    msgcache::plan_cache(c.mc_plan, &c.mc_tab->ix);
+  }
   *cached = true;
   return true;
 }
@@ -1608,7 +1650,17 @@ void mc_finish(Ctx &c, const int32_t *seg_verdicts, bool all_ok) {
   }
   msgcache::plan_verdicts(sp, seg_verdicts ? seg_ok.data() : nullptr, all_ok);
   std::lock_guard<std::mutex> lk(mcache.mu);
+  const uint64_t before = mcache.st[msgcache::PUBLISHED];
   tab->ix.finish(sp.txn, sp.ok.data());
+  if (c.mc_checks) mcache.cst[3] += mcache.st[msgcache::PUBLISHED] - before;
+}
+
+// per-check calls that gbls_msgcache_serve_checks does not serve (messages of other lengths,
+// registry-indexed and _device checks) count their checks as bypassed, as a sliced submission does
+void mc_checks_unserved(size_t m) {
+  if (!mcache.on.load(std::memory_order_relaxed) || !mcache.serve_checks.load(std::memory_order_relaxed)) return;
+  std::lock_guard<std::mutex> lk(mcache.mu);
+  if (mcache.slots) mcache.st[msgcache::BYPASSED] += m;
 }
 
 // One device: host batch [sets b..e) in segments seg (rebased, host) -> per-segment
@@ -1636,9 +1688,19 @@ bool enqueue_host_batch(Ctx &c, Device &d, const uint8_t *msgs, const g2a *sigs,
   msgcache::ShardPlan &sp = c.mc_plan;
   bool cached = false;
   if (sp.txn.active) mc_finish(c, nullptr, false);  // (never: every call ends in mc_finish)
+  c.mc_checks = false;
   if (!single && n > 0 && mcache.on.load(std::memory_order_relaxed)) {
     msgcache::plan_groups(sp, msgs + 32 * b, n, seg, nseg);
     if (!mc_plan_shard(c, d, lines_unsliced(sp.U, n, seg, nseg), n, &cached)) return false;
+  } else if (single && n > 0 && n == nseg && mcache.on.load(std::memory_order_relaxed) &&
+             mcache.serve_checks.load(std::memory_order_relaxed)) {
+    // per-check calls (gbls_msgcache_serve_checks): one pair per check, a missed message hashed
+    // once.  The grouped regime (pipeline_verdicts) is not served and counts as a sliced submission
+    bool plain = g.per_check.load() || !verdicts || n < kGroupMinChecks || n > kGroupMaxChecks;
+    for (size_t s = 0; plain && s <= nseg; s++) plain = seg[s] == s;
+    c.mc_checks = true;
+    if (plain) msgcache::plan_groups(sp, msgs + 32 * b, n, seg, nseg);  // U == n: group q is check q
+    if (!mc_plan_shard(c, d, plain && lines_unsliced(n, n, seg, nseg), n, &cached)) return false;
   }
   if (!cached && !single && n > 1 && g.dedup.load(std::memory_order_relaxed)) {
     dedup::build(plan, msgs + 32 * b, n, seg, nseg);
@@ -2258,6 +2320,7 @@ static int single_checks(const g2a *sigs, const uint8_t *msg_data, const uint32_
   if (mode && !valid_offsets(seg_off, m, seg_off ? seg_off[m] : 0))
     return fail(GBLS_ERR_ARG), FAILED;
   size_t nkeys = mode ? seg_off[m] : m;
+  mc_checks_unserved(m);
   std::shared_lock<std::shared_mutex> rl(g.reg_mu);
   Device &d = pick_device();
   Lease L(d);
@@ -2582,6 +2645,7 @@ int gbls_fast_aggregate_verify_indexed_device(const gbls_p2_affine *sigs, const 
   if (m == 0) return GBLS_SUCCESS;
   Device *d = current_device();
   if (!d) return fail(GBLS_ERR_ARG), FAILED;
+  mc_checks_unserved(m);
   std::shared_lock<std::shared_mutex> rl(g.reg_mu);
   Lease L(*d, true, (hipStream_t)stream);
   Ctx &c = *L;
@@ -3340,6 +3404,111 @@ int gbls_msgcache_stats(uint64_t out[8]) {
     for (auto &d : g.devs)
       if (d->mc_tab && d->mc_tab->gen == mcache.gen) out[6] += d->mc_tab->ix.entries;
   out[7] = 0;
+  return GBLS_SUCCESS;
+}
+
+// ---- include/grandine_bls_gpu_msgcache_checks.h
+int gbls_msgcache_serve_checks(int on) {
+  t_last_error = GBLS_ERR_NONE;
+  return mcache.serve_checks.exchange(on != 0) ? 1 : 0;
+}
+
+int gbls_msgcache_checks_stats(uint64_t out[4]) {
+  t_last_error = GBLS_ERR_NONE;
+  if (!out) return fail(GBLS_ERR_ARG), FAILED;
+  std::lock_guard<std::mutex> lk(mcache.mu);
+  for (int i = 0; i < 4; i++) out[i] = mcache.cst[i];
+  return GBLS_SUCCESS;
+}
+
+// One engine device's part of a prefetch: the lines of the messages dp.fill_msgs into the slots
+// dp.fill_slot of table `tab`, enqueued on the context's main stream in pieces that keep every
+// event of a piece's pairs resident (the line budget).  The pipeline's miss prefix, then the store.
+static bool prefetch_enqueue(Ctx &c, const msgcache::DevicePrefetch &dp, uint32_t *tab) {
+  hipStream_t st = c.own;
+  const size_t F = dp.fill.size();
+  if (!c.begin(st)) return false;
+  if (!F) return true;
+  const size_t piece = std::min(F, std::max<size_t>(1, g.line_budget / (msgcache::kSlotWords * 4)));
+  if (!c.upload_staged(c.in0, dp.fill_msgs.data(), 32 * F, st)) return false;
+  // [pairs of a piece: 0 .. piece)[the F slots]
+  std::vector<uint32_t> &t = c.host_tab;
+  t.resize(piece + F);
+  for (size_t i = 0; i < piece; i++) t[i] = (uint32_t)i;
+  std::copy(dp.fill_slot.begin(), dp.fill_slot.end(), t.begin() + piece);
+  if (!c.ensure(c.U, 2 * piece * sizeof(fp2) + 16) || !c.ensure(c.Q, 2 * piece * sizeof(g2j) + 16) ||
+      !c.ensure(c.H, piece * sizeof(g2a)) || !c.ensure(c.lines, piece * msgcache::kSlotWords * 4) ||
+      !c.upload_staged(c.tab, t.data(), t.size() * 4, st))
+    return false;
+  const uint32_t *T = c.tab.as<uint32_t>();
+  for (size_t at = 0; at < F; at += piece) {
+    const uint32_t nm = (uint32_t)std::min(piece, F - at);
+    const LineCols lc{nullptr, nm};  // pair i in column i
+    set_side_hash(c, st, c.in0.as<uint8_t>() + 32 * at, nullptr, nm);
+    set_side_lines(c, st, nm, nm <= kW4Max, lc, ML_EVENTS);
+    StageTimer tm(S_LC_STORE, st);
+    launch_linecache_store(st, tab, T, T + piece + at, nm, lc, c.lines.as<uint32_t>());
+  }
+  HIPCHK(hipGetLastError());
+  return true;
+}
+
+int gbls_msgcache_prefetch(const uint8_t (*msgs)[32], size_t n, int32_t *status) {
+  if (status) fill(status, n, GBLS_PREFETCH_SKIPPED);
+  t_last_error = GBLS_ERR_NONE;
+  if (n == 0) return GBLS_SUCCESS;
+  if (!msgs || n > 0xffffffffu) return fail(GBLS_ERR_ARG), FAILED;
+  if (!mcache.on.load()) return GBLS_SUCCESS;  // cache off: every status SKIPPED, no device work
+  if (!ensure_ready()) return FAILED;
+  msgcache::Prefetch pf;
+  msgcache::prefetch_groups(pf, &msgs[0][0], n);
+  const size_t ndev = g.devs.size();
+  std::vector<msgcache::DevicePrefetch> dps(ndev);
+  std::vector<std::shared_ptr<McTable>> tabs(ndev);
+  std::vector<std::unique_ptr<Lease>> leases;
+  bool ok = true, on = true;
+  for (size_t j = 0; j < ndev && ok && on; j++) {
+    Device &d = *g.devs[j];
+    leases.emplace_back(new Lease(d, 0));  // a normal-class context, never a block-class one
+    Lease &L = *leases.back();
+    if (!L.ok()) {
+      ok = false;
+      break;
+    }
+    {
+      std::shared_ptr<McTable> old;  // a replaced table is released outside the lock
+      std::lock_guard<std::mutex> lk(mcache.mu);
+      if (!mcache.slots) {  // switched off meanwhile
+        on = false;
+        break;
+      }
+      if (!mc_table(d, &old)) {
+        ok = false;
+        break;
+      }
+      tabs[j] = d.mc_tab;
+      msgcache::prefetch_lookup(dps[j], tabs[j]->ix, pf, msgcache::spare_for(mcache.slots));
+    }
+    ok = prefetch_enqueue(*L, dps[j], tabs[j]->dev);
+  }
+  for (auto &L : leases)
+    if ((*L)->active && hipStreamSynchronize((*L)->own) != hipSuccess) ok = fail(GBLS_ERR_HIP);
+  // every device's transaction ends: published only if every device's work is done
+  std::vector<int32_t> ust(pf.D, GBLS_PREFETCH_SKIPPED), dev(pf.D);
+  {
+    std::lock_guard<std::mutex> lk(mcache.mu);
+    size_t merged = 0;
+    for (size_t j = 0; j < ndev; j++) {
+      if (!tabs[j]) continue;
+      msgcache::prefetch_finish(dps[j], tabs[j]->ix, pf, ok && on, dev.data());
+      msgcache::merge_status(ust.data(), dev.data(), pf.D, merged++ == 0);
+    }
+    if (!ok || !on || merged != ndev) std::fill(ust.begin(), ust.end(), (int32_t)GBLS_PREFETCH_SKIPPED);
+    for (int32_t v : ust) mcache.cst[0] += v == GBLS_PREFETCH_ENTERED;
+  }
+  tabs.clear();
+  if (!ok) return FAILED;
+  if (status) msgcache::prefetch_scatter(pf, ust.data(), status);
   return GBLS_SUCCESS;
 }
 

@@ -103,8 +103,8 @@ struct Index {
     return kNone;
   }
   // D DISTINCT messages: hit[i] = 1 and slot[i] = the pinned entry, or hit[i] = 0 and slot[i] = the
-  // taken slot the call writes the lines to (kNone: none to spare)
-  void plan(Txn &t, const uint8_t *msgs, size_t D, uint8_t *hit, uint32_t *slot) {
+  // taken slot the call writes the lines to (kNone: none to spare, or max_take slots taken already)
+  void plan(Txn &t, const uint8_t *msgs, size_t D, uint8_t *hit, uint32_t *slot, size_t max_take = SIZE_MAX) {
     t.reset();
     t.active = true;
     t.epoch = epoch;
@@ -121,7 +121,8 @@ struct Index {
       } else {
         st[MISSES]++;
         hit[i] = 0;
-        if (!free_.empty()) {
+        if (!free_.empty() && max_take) {
+          max_take--;
           s = free_.back();
           free_.pop_back();
           state[s] = TAKEN;
@@ -135,17 +136,21 @@ struct Index {
     }
   }
   // after the call's host synchronisation.  ok (nullable: none): per miss of t.take, whether its
-  // verdict was GBLS_SUCCESS
-  void finish(Txn &t, const uint8_t *ok) {
+  // verdict was GBLS_SUCCESS.  entered (nullable, per miss of t.take): whether the message was an
+  // entry right after its turn (published, or present meanwhile), whatever a later one evicts
+  void finish(Txn &t, const uint8_t *ok, uint8_t *entered = nullptr) {
     if (!t.active) return;
     for (uint32_t s : t.hit) unpin(s);
     for (size_t j = 0; j < t.take.size(); j++) {
       const uint32_t s = t.take[j];
+      if (entered) entered[j] = 0;
       if (s == kNone) continue;
-      if (ok && ok[j] && t.epoch == epoch)
+      if (ok && ok[j] && t.epoch == epoch) {
         publish(s);
-      else
+        if (entered) entered[j] = find(&key[(size_t)s * 32]) != kNone;  // (a returned slot keeps its key)
+      } else {
         release(s);
+      }
     }
     t.reset();
   }
@@ -250,6 +255,9 @@ struct ShardPlan {
   std::vector<uint8_t> miss_msgs;  // M x 32, in pair order
   std::vector<uint32_t> csr;       // [off (U + 1)][sets (n)] of the groups in PAIR order (k_g1s_msgsum)
   std::vector<uint32_t> hit_slot;  // U - M: the slot of pair M + k
+  // per-check plans (gbls_msgcache_checks.h): the last ncopy of those pairs carry a message that
+  // missed; they load from the slot its first pair fills, after that store.  0 in a shard plan
+  uint32_t ncopy = 0;
   std::vector<uint32_t> store_pair, store_slot;  // the miss pairs that have a slot to fill
   std::vector<uint8_t> seg_ok;     // per segment: its verdict was GBLS_SUCCESS (the caller's, for plan_verdicts)
   std::vector<uint8_t> ok;         // per txn.take entry (finish)
@@ -288,6 +296,7 @@ inline void plan_cache(ShardPlan &p, Index *ix) {
   const dedup::Plan &g = p.groups;
   const uint32_t U = p.U;
   const size_t n = g.n, nseg = g.nseg;
+  p.ncopy = 0;
   p.uhit.assign(p.D, 0);
   p.uslot.assign(p.D, kNone);
   if (ix)

@@ -29,9 +29,11 @@ pub mod ffi_committees;
 pub mod ffi_each;
 pub mod ffi_local;
 pub mod ffi_msgcache;
+pub mod ffi_msgcache_checks;
 pub mod ffi_spans;
 pub mod local;
 pub mod msgcache;
+pub mod msgcache_checks;
 pub mod spans;
 
 use core::{ffi::c_int, ptr};

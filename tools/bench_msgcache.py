@@ -29,6 +29,13 @@ call time.  CALLS is chosen per shape so that a run's timed window is about --wi
         # call (gbls_profile), and the bytes/s of the load and store kernels at 4096 messages
   python tools/bench_msgcache.py --plan-cost EXE       # the host cost of the plan, by
         # tests/native/msgcache_index_main.cpp built -O2
+  python tools/bench_msgcache.py --checks              # per-check calls and prefetch
+        # (include/grandine_bls_gpu_msgcache_checks.h), us per call: verify1 (gbls_verify), fav512
+        # (one gbls_fast_aggregate_verify over 512 keys), each64x4 (gbls_verify_batch_compressed,
+        # 64 checks on 4 roots, one bad), legs off (serving off, the cache on), cold and warm
+        # (serving on); prefetch4 and prefetch64: the prefetch call's own time, and the first
+        # 64-set gbls_multi_verify after it against the same call cold.  With --compare the other
+        # library's "off" leg is the parent's figure; --stages adds the per-stage device times
 Every child process runs under a time limit, and the first failure stops the tool.
 """
 import argparse
@@ -164,6 +171,134 @@ def stages(a, G, F, L):
     L.gbls_msgcache_configure(0)
 
 
+CHECK_SHAPES = ["verify1", "fav512", "each64x4"]
+
+
+def check_shape(G, F, L, name):
+    """-> (call() -> rc, expected rc, checks)"""
+    seed = b"bench-msgcache/" + name.encode()
+    if name == "verify1":
+        msgs, comp, pks, _ = make_shape(G, F, L, 1, 1, seed)
+        sks = F.seeded_sks(1, seed)
+        sig = G.buf(F.sign(sks, msgs))
+        return (lambda: L.gbls_verify(sig, msgs, 32, pks)), 0, 1
+    if name == "fav512":
+        msg = F.messages(1, seed)
+        sks = F.seeded_sks(512, seed)
+        sig = G.buf(F.sign([sum(sks) % F.R_ORDER], msg))
+        pks = G.buf(F.public_keys(sks))
+        return (lambda: L.gbls_fast_aggregate_verify(sig, msg, 32, pks, 512)), 0, 1
+    msgs, comp, pks, _ = make_shape(G, F, L, 64, 4, seed)
+    comp = comp[:96 * 9] + comp[96 * 10:96 * 11] + comp[96 * 10:]  # check 9 carries check 10's signature
+    st, v = G.i32_array(64), G.i32_array(64)
+    return (lambda: L.gbls_verify_batch_compressed(msgs, comp, pks, None, 64, st, v)), 0, 64
+
+
+def checks_worker(a):
+    from grandine_amd import _lib as G
+    from grandine_amd import factory as F
+    L = G.lib()
+    serves = hasattr(L, "gbls_msgcache_serve_checks")
+    legs = ["off"] + (["cold", "warm"] if serves else [])
+    print(json.dumps({"library": os.path.relpath(G.LIB_PATH, ROOT), "version": L.gbls_version().decode(),
+                      "serves_checks": serves, "legs": legs}), flush=True)
+    want = set(a.shapes.split(",")) if a.shapes else None
+    names = [L.gbls_stage_name(k).decode() for k in range(32) if L.gbls_stage_name(k)]
+    ms, ncalls = (ctypes.c_double * 32)(), (ctypes.c_uint32 * 32)()
+
+    def set_leg(leg):
+        if serves:
+            L.gbls_msgcache_serve_checks(0 if leg == "off" else 1)
+
+    def timed(fn, expect, clear):
+        if clear:
+            L.gbls_msgcache_clear()
+        t0 = time.perf_counter()
+        rc = fn()
+        dt = time.perf_counter() - t0
+        if rc != expect:
+            raise SystemExit("rc=%d, expected %d" % (rc, expect))
+        return dt
+
+    def measure(legs_, fns, n):
+        """fns: leg -> (fn, expected rc, clear before each call)."""
+        figures = {leg: [] for leg in legs_}
+        calls = 0
+        for run in range(a.runs):
+            for leg in (legs_ if run % 2 == 0 else legs_[::-1]):
+                set_leg(leg)
+                fn, expect, clear = fns[leg]
+                warm = [timed(fn, expect, clear) for _ in range(a.warmup)]
+                if not calls:
+                    calls = int(max(20, min(2000, a.window / max(statistics.median(warm), 1e-6))))
+                figures[leg].append(statistics.median(timed(fn, expect, clear) for _ in range(calls)) * 1e6)
+        out = {"calls_per_run": calls}
+        for leg in legs_:
+            out[leg] = summary(figures[leg], n)
+        return out
+
+    def stage_times(fn, expect, clear):
+        L.gbls_profile(1)
+        L.gbls_profile_reset()
+        for _ in range(20):
+            timed(fn, expect, clear)
+        L.gbls_profile_read(ms, ncalls, 32)
+        L.gbls_profile(0)
+        return {nm: round(ms[k] / 20 * 1e3, 1) for k, nm in enumerate(names) if ncalls[k]}  # us per call
+
+    G.check(L.gbls_msgcache_configure(CACHE_SLOTS), "configure")
+    try:
+        for name in CHECK_SHAPES:
+            if want and name not in want:
+                continue
+            fn, expect, n = check_shape(G, F, L, name)
+            fns = {"off": (fn, expect, False), "cold": (fn, expect, True), "warm": (fn, expect, False)}
+            res = {"shape": name, "sets": n}
+            res.update(measure(legs, fns, n))
+            if a.stages:
+                for leg in legs:
+                    set_leg(leg)
+                    res["stages:" + leg] = stage_times(*fns[leg])
+            print(json.dumps(res), flush=True)
+        if serves:
+            set_leg("off")
+            for name, k in (("prefetch4", 4), ("prefetch64", 64)):
+                if want and name not in want:
+                    continue
+                msgs, comp, pks, rands = make_shape(G, F, L, 64, k, b"bench-msgcache/" + name.encode())
+                roots = msgs[:32 * k]
+                st = G.i32_array(64)
+
+                def verify():
+                    return L.gbls_multi_verify_compressed_ex(msgs, comp, pks, None, None, rands, 64, st, 0)
+
+                def after_prefetch():  # the clear and the prefetch are outside the timed window of `first`
+                    L.gbls_msgcache_clear()
+                    return L.gbls_msgcache_prefetch(roots, k, None)
+
+                first_figs = {"prefetch": [], "first_after": [], "first_cold": []}
+                for run in range(a.runs):
+                    for _ in range(a.warmup):
+                        after_prefetch()
+                        verify()
+                    pf, fa, fc = [], [], []
+                    for _ in range(max(20, int(a.window / 2e-3))):
+                        L.gbls_msgcache_clear()
+                        pf.append(timed(lambda: L.gbls_msgcache_prefetch(roots, k, None), 0, False))
+                        fa.append(timed(verify, 0, False))
+                        fc.append(timed(verify, 0, True))
+                    for key, v in (("prefetch", pf), ("first_after", fa), ("first_cold", fc)):
+                        first_figs[key].append(statistics.median(v) * 1e6)
+                res = {"shape": name, "sets": 64, "distinct": k}
+                for key, v in first_figs.items():
+                    res[key] = summary(v, 64)
+                print(json.dumps(res), flush=True)
+    finally:
+        if serves:
+            L.gbls_msgcache_serve_checks(0)
+        L.gbls_msgcache_configure(0)
+
+
 def plan_cost(exe):
     out = {}
     for n, distinct in ((64, 4), (65536, 1000)):
@@ -184,7 +319,8 @@ def compare(a):
             if path:
                 env["GBLS_LIB"] = path
             cmd = [sys.executable, os.path.abspath(__file__), "--runs", str(a.runs), "--warmup", str(a.warmup),
-                   "--window", str(a.window)] + (["--shapes", a.shapes] if a.shapes else [])
+                   "--window", str(a.window)] + (["--shapes", a.shapes] if a.shapes else []) + (
+                       ["--checks"] if a.checks else [])
             out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=a.child_timeout)
             if out.returncode != 0:
                 raise SystemExit("%s process failed (rc %d):\n%s" % (tag, out.returncode, out.stderr[-2000:]))
@@ -192,10 +328,11 @@ def compare(a):
                 r = json.loads(ln)
                 if "shape" not in r:
                     continue
-                slot = pooled.setdefault(r["shape"], {"shape": r["shape"], "sets": r["sets"], "distinct": r["distinct"]})
-                for leg in ("off", "off+dedup", "cold", "warm"):
-                    if leg in r:
-                        slot.setdefault(tag + ":" + leg, []).extend(r[leg]["runs_us"])
+                slot = pooled.setdefault(r["shape"], {"shape": r["shape"], "sets": r["sets"],
+                                                      "distinct": r.get("distinct")})
+                for leg, v in r.items():
+                    if isinstance(v, dict) and "runs_us" in v:
+                        slot.setdefault(tag + ":" + leg, []).extend(v["runs_us"])
     for name, slot in pooled.items():
         res = {k: (summary(v, slot["sets"]) if isinstance(v, list) else v) for k, v in slot.items()}
         for k, v in res.items():
@@ -213,6 +350,7 @@ def main():
     ap.add_argument("--compare", default="", metavar="LIBDIR", help="another build's directory under grandine_amd/")
     ap.add_argument("--child-timeout", type=float, default=280.0, help="seconds per child process of --compare")
     ap.add_argument("--stages", action="store_true")
+    ap.add_argument("--checks", action="store_true", help="per-check calls and prefetch")
     ap.add_argument("--plan-cost", default="", metavar="EXE")
     a = ap.parse_args()
     if a.plan_cost:
@@ -220,6 +358,8 @@ def main():
         return
     if a.compare:
         return compare(a)
+    if a.checks:
+        return checks_worker(a)
     worker(a)
 
 
