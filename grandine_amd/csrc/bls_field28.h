@@ -136,7 +136,9 @@ HD void mul2(fe &r, const fe &a, const fe &b, const fe &c, const fe &d) {
 }
 
 // x0 y0 + ... + x5 y5 in one reduction (one operand of each pair normalized, the other with
-// limbs < 2^29; values < 34 p^2 in all: output < 1.02 p)
+// limbs < 2^29; values < 34 p^2 in all: output < 1.02 p).  A column holds at most 84 terms
+// < 2^57 and 14 reduction terms < 2^56: 182 x 2^56 < 2^63.51; with x < 1.1 p, y < 5.1 p and
+// every lower limb full the modeled peak is 2^63.33 (tools/ubench/field28_vectors.py)
 HD void mul6(fe &r, const fe &x0, const fe &y0, const fe &x1, const fe &y1, const fe &x2, const fe &y2,
              const fe &x3, const fe &y3, const fe &x4, const fe &y4, const fe &x5, const fe &y5) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -147,6 +149,9 @@ HD void mul6(fe &r, const fe &x0, const fe &y0, const fe &x1, const fe &y1, cons
 #endif
 }
 
+// x0 y0 + ... + x3 y3 in one reduction, the contract of its caller sp_mul_sp_lazy: x_k a line
+// coefficient (normalized, < 1.1 p), y_k a line coefficient, its neg_lazy image or xi times one
+// (limbs < 2^29, < 5.1 p); values < 22.5 p^2 in all: output < 1.01 p; column peak 2^62.76
 HD void mul4(fe &r, const fe &x0, const fe &y0, const fe &x1, const fe &y1, const fe &x2, const fe &y2,
              const fe &x3, const fe &y3) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -728,7 +733,10 @@ HD void fe2_mul3k(fe2 &r, const fe2 &x0, const fe2 &u0, const fe &u0s, const fe2
   fe2_mul3k_dev(r.c0, r.c1, x0.c0, x0.c1, u0.c0, u0.c1, u0s, x1.c0, x1.c1, u1.c0, u1.c1, u1s, x2.c0, x2.c1, u2.c0,
                 u2.c1, u2s);
 #else
-  (void)u0s, (void)u1s, (void)u2s;  // the host computes the same value (mod p) the schoolbook way
+  // the host computes the same value (mod p) the schoolbook way, for u.c1 within neg_lazy's reach
+  // only (limbwise <= the 4p bias; the Miller product's u.c1 is < 2.2 p): the device form takes
+  // the whole contract, u.c1 < 5.1 p (tests/test_gpu_field28.py)
+  (void)u0s, (void)u1s, (void)u2s;
   fe n0, n1, n2;
   neg_lazy(n0, u0.c1);
   neg_lazy(n1, u1.c1);

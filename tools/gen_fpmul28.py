@@ -13,7 +13,9 @@ fe_mul4_dev / fe_mul6_dev: the sum of four / SIX products in one reduction -- on
 sparse Miller product (bls_field28.h fe12_mul_034_lazy: every Fp12 coefficient of f * line is
 a sum of three Fp2 products, i.e. six Fp products per Fp coordinate).  Bound: with one operand
 of each pair normalized (limbs < 2^28) and the other < 2^29, a column holds at most
-14 * (6 * 2^57) + 14 * 2^56 < 2^63.3 (no overflow of the 64-bit accumulator).
+14 * (6 * 2^57) + 14 * 2^56 = 182 * 2^56 < 2^63.51 (no overflow of the 64-bit accumulator); inside
+the value contract (x < 1.1 p, y < 5.1 p, every lower limb full) the modeled peak is 2^63.33
+(tools/ubench/field28_vectors.py, tests/test_field28_vectors.py).
 
 Run:  python tools/gen_fpmul28.py > grandine_amd/csrc/bls_fpmul28_gen.h
 """
@@ -158,7 +160,9 @@ def emit_kara3(w, name):
     B_k is the column of the cross terms x0 u1 + x1 u0 >= 0, < 84 x 2^56); the sums' operands
     have limbs < 2^29, so a column of C is < 42 x 2^58 < 2^63.4 (no overflow of the unsigned
     64-bit accumulator).  Inputs: x_q, u_q normalized (limbs < 2^28); values < 1.1 p (x) and
-    < 5.1 p (u); xs_q / us_q their limbwise sums.  Outputs < 1.03 p, normalized."""
+    < 5.1 p (u); xs_q / us_q their limbwise sums.  Outputs < 1.03 p, normalized.  Modeled peaks
+    inside that contract (tools/ubench/field28_vectors.py): acc1 2^63.29, a and b 2^61.29,
+    |acc0| 2^61.44; the largest sum x_q.c1 u_q.c1 is 16.83 p^2 against the bias of 17 p^2."""
     bias = [(BIAS_KARA >> (28 * k)) & 0xfffffff for k in range(28)]
     assert BIAS_KARA >> (28 * 28) == 0
     Q = 3
