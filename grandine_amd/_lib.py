@@ -134,6 +134,10 @@ EXPORTS_LOCAL = [
     "gbls_verify_items_local",
 ]
 LOCAL_KEYS = 0xFFFFFFFE  # GBLS_LOCAL_KEYS: com[i] of a local set
+# include/grandine_bls_gpu_fold.h (verified folds: the each-call also sums the signatures that passed)
+EXPORTS_FOLD = [
+    "gbls_verify_each_fold",
+]
 # include/grandine_bls_gpu_msgcache.h (message line cache)
 EXPORTS_MSGCACHE = [
     "gbls_msgcache_configure",
@@ -258,6 +262,8 @@ def load_library():
                                                       _vp, _vp]),
                 "gbls_verify_items_local": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp,
                                                        _sz, _vp, _vp, _vp, _vp, _c.c_uint32]),
+                "gbls_verify_each_fold": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp,
+                                                     _vp, _vp, _vp, _vp]),
                 "gbls_msgcache_configure": (_c.c_int, [_sz]),
                 "gbls_msgcache_slots": (_sz, []),
                 "gbls_msgcache_clear": (_c.c_int, []),
@@ -268,10 +274,10 @@ def load_library():
             }
             for name, (res, args) in sig.items():
                 # an experiment build (GBLS_LIB) may predate the message line cache (or its
-                # per-check extension), the bits, the spans, the each or the local calls: A/B tools
+                # per-check extension), the bits, the spans, the each, the local or the fold calls: A/B tools
                 # load it and leave those entries alone; the package's own library must have them
                 if (_override and name in EXPORTS_MSGCACHE + EXPORTS_MSGCACHE_CHECKS + EXPORTS_BITS + EXPORTS_SPANS
-                        + EXPORTS_EACH + EXPORTS_LOCAL and not hasattr(lib, name)):
+                        + EXPORTS_EACH + EXPORTS_LOCAL + EXPORTS_FOLD and not hasattr(lib, name)):
                     continue
                 fn = getattr(lib, name)
                 fn.restype = res

@@ -456,6 +456,40 @@ class Signature:
         return [(st[i], kst[i], v[i] == G.SUCCESS) for i in range(n)]
 
     @staticmethod
+    def verify_each_fold(messages: Iterable[bytes], signature_bytes: Iterable[bytes], base_slots: Iterable[int],
+                         committee_bits: Iterable[bytes], bitfields: Iterable[bytes],
+                         validator_indices: Iterable[Sequence[int]], groups: Iterable[Sequence[int]]):
+        """verify_each_spans which also sums the signatures that passed (gbls_verify_each_fold):
+        ``groups[g]`` lists sets of this call (a set may be in several groups, and more than once in
+        one).  Returns (per set (signature status, key status, ok), per group (Signature, count,
+        SignatureBytes)): the sum of the decoded signatures of the group's sets that verified, how
+        many occurrences entered it (0: nothing passed) and the sum compressed.  The sums are
+        computed on the device behind the verdicts, in the same submission."""
+        args, n = Signature._span_sets(messages, signature_bytes, base_slots, committee_bits, bitfields,
+                                       validator_indices)
+        grp = [[int(s) for s in g] for g in groups]
+        if any(s < 0 or s >= n for g in grp for s in g):
+            raise ValueError("a group names sets of this call")
+        nfold = len(grp)
+        if n == 0 and nfold == 0:
+            return [], []
+        foff = [0]
+        for g in grp:
+            foff.append(foff[-1] + len(g))
+        flat = [s for g in grp for s in g]
+        L = G.lib()
+        st, kst, v = G.i32_array(n), G.i32_array(n), G.i32_array(n)
+        out = ctypes.create_string_buffer(G.P2_BYTES * max(nfold, 1))
+        fb = ctypes.create_string_buffer(96 * max(nfold, 1))
+        cnt = G.u32_array([0] * nfold)
+        G.check(L.gbls_verify_each_fold(*args, n, G.u32_array(flat or [0]), G.u32_array(foff), nfold, st, kst, v,
+                                        out, fb, cnt), "gbls_verify_each_fold")
+        sets = [(st[i], kst[i], v[i] == G.SUCCESS) for i in range(n)]
+        folds = [(Signature(out.raw[G.P2_BYTES * g:G.P2_BYTES * (g + 1)]), cnt[g],
+                  SignatureBytes(fb.raw[96 * g:96 * (g + 1)])) for g in range(nfold)]
+        return sets, folds
+
+    @staticmethod
     def verify_items_spans(messages: Iterable[bytes], signature_bytes: Iterable[bytes], base_slots: Iterable[int],
                            committee_bits: Iterable[bytes], bitfields: Iterable[bytes],
                            validator_indices: Iterable[Sequence[int]], item_offsets: Sequence[int],

@@ -41,6 +41,7 @@
 #include "../../include/grandine_bls_gpu_each.h"
 #include "../../include/grandine_bls_gpu_spans.h"
 #include "../../include/grandine_bls_gpu_local.h"
+#include "../../include/grandine_bls_gpu_fold.h"
 #include "gbls_common.h"
 #include "gbls_bits.h"
 #include "gbls_committees.h"
@@ -51,6 +52,7 @@
 #include "gbls_sched.h"
 #include "gbls_spans.h"
 #include "gbls_local.h"
+#include "gbls_fold.h"
 #include "gbls_tables.h"
 
 using namespace gbls;
@@ -138,13 +140,13 @@ struct Buf {
 // ---- optional per-stage timing (HIP events on the launch stream), for bench.py
 enum Stage {
   S_H2C_FIELD, S_H2C_MAP, S_H2C_CLEAR, S_G1MUL, S_G2MUL, S_G2SUM, S_LINES, S_LINES_S, S_ML_LEAF,
-  S_ML_REDUCE, S_ML_HORNER, S_FINAL, S_PK_GATHER, S_MSM, S_MSGSUM, S_LC_LOAD, S_LC_STORE, S_COUNT
+  S_ML_REDUCE, S_ML_HORNER, S_FINAL, S_PK_GATHER, S_MSM, S_MSGSUM, S_LC_LOAD, S_LC_STORE, S_FOLD, S_COUNT
 };
 const char *kStageNames[S_COUNT] = {"k_h2c_field", "k_h2c_map",   "k_h2c_clear", "k_mv_g1mul",
                                     "k_mv_g2mul",  "k_g2sum",      "k_lines",     "k_lines_S",
                                     "k_ml_group",  "k_ml_reduce",  "k_ml_horner", "k_final_verdict",
                                     "k_pk_resolve", "k_msm",        "k_g1s_msgsum", "k_linecache_load",
-                                    "k_linecache_store"};
+                                    "k_linecache_store", "k_g2_fold"};
 
 // GBLS_TRACE_STALLS=1: report host waits inside device entry points (diagnostics); every line
 // carries the call index (leases since gbls_init) and whether the lease created its context
@@ -259,7 +261,8 @@ struct Ctx {
   bool used = false;                  // last_stream is meaningful
   hipStream_t last_stream = nullptr;  // main stream of the previous call
   Buf in0, in1, in2, in3, in4, in5, U, Q, H, P, Pc, R, Sj, gpart, lines, Ts, V0, V1, V28, hparts, tab, part, err, out0,
-      out1, pks, pre, pre2, msm, sigd, sigst, rnd, ng1, gerr, gv, redo, rtab, in6, Pset, in7, in8, spj, spf, in9, loc, locst;
+      out1, pks, pre, pre2, msm, sigd, sigst, rnd, ng1, gerr, gv, redo, rtab, in6, Pset, in7, in8, spj, spf, in9, loc, locst,
+      fin, fout;  // verified folds: the groups' CSR, and [points][counts][bytes] per group
   // per-call option of the next pipeline_partials on this lease: compressed signatures
   // (96 B each, device) to decompress on the signature-side stream into `sigs`, with their
   // BLST_ERROR statuses (device) failing their segments (consumed and reset by the pipeline)
@@ -1719,6 +1722,20 @@ bool enqueue_host_batch(Ctx &c, Device &d, const uint8_t *msgs, const g2a *sigs,
     return false;
   }
   if (!single && !c.upload_staged(c.in3, rands + b, n * 8, st)) return false;
+  // verified folds: the groups' CSR [fold_off (nfold + 1)][fold_set] goes up with the inputs; the
+  // fold itself runs behind the verdicts (below).  The whole call is this one shard (verify_host).
+  const size_t nfold = src.nfold, fold_cnt = nfold ? src.fold_off[nfold] : 0;
+  const size_t fold_pts = nfold * sizeof(g2a), fold_words = nfold * 4;
+  if (nfold) {
+    if (!single || !verdicts || b != 0 || n != nseg || !src.fold_out || !src.fold_count) return fail(GBLS_ERR_ARG);
+    const size_t csr_bytes = (nfold + 1 + fold_cnt) * 4;
+    if (!c.ensure(c.fin, csr_bytes + 16) || !c.ensure(c.fout, fold_pts + fold_words + 96 * nfold + 16)) return false;
+    uint32_t *stage = static_cast<uint32_t *>(c.staging(csr_bytes));
+    if (!stage) return fail(GBLS_ERR_HIP);
+    std::memcpy(stage, src.fold_off, (nfold + 1) * 4);
+    if (fold_cnt) std::memcpy(stage + nfold + 1, src.fold_set, fold_cnt * 4);
+    if (!c.send_staged(c.fin.p, stage, csr_bytes, st)) return false;
+  }
   const g2a *dsigs;
   if (sigs_c) {  // compressed: decompressed on the device by the pipeline (side stream 2)
     if (!c.upload_staged(c.in1, sigs_c + 96 * b, 96 * n, st) ||
@@ -1754,6 +1771,23 @@ bool enqueue_host_batch(Ctx &c, Device &d, const uint8_t *msgs, const g2a *sigs,
   c.plan = nullptr;
   c.mc = nullptr;
   if (!ok) return false;
+  if (nfold) {
+    // behind the point where the per-set verdicts are final on the device (the per-check final
+    // exponentiation, or the grouped regime's last re-check pass): the device verdicts and the
+    // decoded signatures, both in set order, no host synchronisation
+    uint8_t *fo = c.fout.as<uint8_t>();
+    {
+      StageTimer t(S_FOLD, st);
+      launch_g2_fold(st, dsigs, c.out1.as<int32_t>(), c.fin.as<uint32_t>() + nfold + 1, c.fin.as<uint32_t>(),
+                     (uint32_t)nfold, reinterpret_cast<g2a *>(fo), src.fold_bytes ? fo + fold_pts + fold_words : nullptr,
+                     reinterpret_cast<uint32_t *>(fo + fold_pts));
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(src.fold_out, fo, fold_pts, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(src.fold_count, fo + fold_pts, fold_words, hipMemcpyDeviceToHost, st));
+    if (src.fold_bytes)
+      HIPCHK(hipMemcpyAsync(&src.fold_bytes[0][0], fo + fold_pts + fold_words, 96 * nfold, hipMemcpyDeviceToHost, st));
+  }
   if (verdicts) {
     HIPCHK(hipMemcpyAsync(verdicts, c.out1.p, nseg * 4, hipMemcpyDeviceToHost, st));
   } else {
@@ -1836,8 +1870,10 @@ bool verify_host(const uint8_t *msgs, const g2a *sigs, const uint8_t *sigs_c, in
     return ok;
   }
   // ---- whole segments per device, contiguous groups balanced by set count
+  // a submission that carries fold groups stays on one engine: a group may name sets anywhere in
+  // the call
   size_t k = 1;
-  if (ndev > 1 && nseg > 1) k = std::min({ndev, nseg, std::max<size_t>(1, n / kShardMinSets)});
+  if (ndev > 1 && nseg > 1 && !src.nfold) k = std::min({ndev, nseg, std::max<size_t>(1, n / kShardMinSets)});
   std::vector<size_t> cut(k + 1, 0);  // segment boundaries of the groups
   cut[k] = nseg;
   for (size_t j = 1; j < k; j++) {
@@ -3169,19 +3205,32 @@ int gbls_multi_verify_spans(const uint8_t (*msgs)[32], const uint8_t (*sigs)[96]
 // are one coalescer request over a host span source: nseg segments of a random-linear-combination
 // batch (rands), or n independent single checks (rands == nullptr, identity segments), with the
 // signatures' and the keys' statuses read back beside the verdicts.
+// fold (gbls_verify_each_fold only, with each): the call's groups and fold outputs
+// (include/grandine_bls_gpu_fold.h), in a KeySource's fold fields; the request is then of the fold kind.
 static int spans_checks_co(const uint8_t (*msgs)[32], const uint8_t (*sigs)[96], const uint32_t *com,
                            const uint8_t (*cbits)[8], const uint8_t *bits, const uint32_t *bits_off,
                            const uint32_t *pk_idx, const uint32_t *pk_off, const uint64_t *rands, size_t n,
                            const uint32_t *seg_off, size_t nseg, int32_t *sig_status, int32_t *key_status,
-                           int32_t *verdicts, uint32_t call_flags, bool each) {
+                           int32_t *verdicts, uint32_t call_flags, bool each, const PkSource *fold = nullptr) {
+  // (a group count that does not fit 32 bits names no array to fill)
+  const size_t nfold = fold && (uint64_t)fold->nfold < 0xffffffffull ? fold->nfold : 0;
   auto prefill = [&] {
     if (verdicts) fill(verdicts, nseg, GBLS_VERIFY_FAIL);
     if (sig_status) fill(sig_status, n, GBLS_BAD_ENCODING);
     if (key_status) fill(key_status, n, GBLS_BAD_ENCODING);
+    if (!nfold) return;
+    if (fold->fold_out) std::memset(fold->fold_out, 0, nfold * sizeof(g2a));
+    if (fold->fold_count) std::memset(fold->fold_count, 0, nfold * sizeof(uint32_t));
+    for (size_t g = 0; fold->fold_bytes && g < nfold; g++) {
+      std::memset(fold->fold_bytes[g], 0, 96);
+      fold->fold_bytes[g][0] = 0xc0;
+    }
   };
   prefill();
   API_BEGIN
-  if (n == 0 || nseg == 0) return GBLS_SUCCESS;
+  if (fold && !fold_args_ok(fold->fold_set, fold->fold_off, fold->nfold, n, fold->fold_out, fold->fold_count))
+    return fail(GBLS_ERR_ARG), FAILED;
+  if (n == 0 || nseg == 0) return GBLS_SUCCESS;  // (every group is then empty: count 0, infinity -- the pre-fill)
   if (!msgs || !sigs || !sig_status || !key_status || !verdicts ||
       !spans_args_ok(com, cbits, bits, bits_off, pk_idx, pk_off, n))
     return fail(GBLS_ERR_ARG), FAILED;
@@ -3193,7 +3242,7 @@ static int spans_checks_co(const uint8_t (*msgs)[32], const uint8_t (*sigs)[96],
   } else if (!rands || !valid_offsets(seg_off, nseg, n)) {
     return fail(GBLS_ERR_ARG), FAILED;
   }
-  CoReq r{&msgs[0][0], nullptr, PkSource(), rands, n, seg_off, nseg, verdicts};
+  CoReq r{&msgs[0][0], nullptr, fold ? *fold : PkSource(), rands, n, seg_off, nseg, verdicts};
   r.src.com = com;
   r.src.cbits = cbits;
   r.src.bits = bits;
@@ -3227,6 +3276,26 @@ int gbls_verify_items_spans(const uint8_t (*msgs)[32], const uint8_t (*sigs)[96]
                             int32_t *verdicts, uint32_t call_flags) {
   return spans_checks_co(msgs, sigs, com, cbits, bits, bits_off, pk_idx, pk_off, rands, n, seg_off, nseg,
                          sig_status, key_status, verdicts, call_flags, false);
+}
+
+// ---- verified folds (include/grandine_bls_gpu_fold.h): the each-call's request with groups of its
+// own sets, a kind of its own in the coalescer.  nfold == 0: the each-call's outputs, no further kernel.
+int gbls_verify_each_fold(const uint8_t (*msgs)[32], const uint8_t (*sigs)[96], const uint32_t *com,
+                          const uint8_t (*cbits)[8], const uint8_t *bits, const uint32_t *bits_off,
+                          const uint32_t *pk_idx, const uint32_t *pk_off, size_t n, const uint32_t *fold_set,
+                          const uint32_t *fold_off, size_t nfold, int32_t *sig_status, int32_t *key_status,
+                          int32_t *verdicts, gbls_p2_affine *fold_out, uint8_t (*fold_bytes)[96],
+                          uint32_t *fold_count) {
+  PkSource fold;
+  fold.fold = true;
+  fold.fold_set = fold_set;
+  fold.fold_off = fold_off;
+  fold.nfold = nfold;
+  fold.fold_out = fold_out;
+  fold.fold_bytes = fold_bytes;
+  fold.fold_count = fold_count;
+  return spans_checks_co(msgs, sigs, com, cbits, bits, bits_off, pk_idx, pk_off, nullptr, n, nullptr, n, sig_status,
+                         key_status, verdicts, 0, true, &fold);
 }
 
 // ---- local key sets (include/grandine_bls_gpu_local.h): the span calls with a call-local table of

@@ -80,6 +80,14 @@ void launch_g1_aggregate_seg(hipStream_t st, const g1a *pks, const uint32_t *off
                              g1a *out, int32_t *status);
 void launch_g2_aggregate_seg(hipStream_t st, const g2a *pts, const uint32_t *off, uint32_t nseg,
                              g2a *out, int32_t *status);
+// segmented aggregations of at least this many segments run one 16-lane row per segment
+// (k_aggregate_rows), fewer one 256-lane workgroup each; the verified folds switch at the same count
+constexpr uint32_t kRowAggregateMinSegs = 128;
+// k_fold.hip -- verified folds (gbls_fold.h): out[g] / count[g] / bytes[96 g] (bytes nullable) = the
+// sum, the number and the compressed sum of sigs[s] over the entries s = set[off[g] .. off[g+1])
+// with verdicts[s] == 0, groups [0, nfold)
+void launch_g2_fold(hipStream_t st, const g2a *sigs, const int32_t *verdicts, const uint32_t *set,
+                    const uint32_t *off, uint32_t nfold, g2a *out, uint8_t *bytes, uint32_t *count);
 // validator registry (f1): keys by index
 void launch_g1_aggregate_idx(hipStream_t st, const g1a *reg, uint32_t nreg, const uint32_t *idx,
                              const uint32_t *off, uint32_t nseg, g1a *out, int32_t *status);

@@ -148,7 +148,30 @@ struct KeySource {
   const G1 *loc = nullptr;
   int32_t *loc_st = nullptr;
   uint32_t loc_np = 0, loc_max_len = 0;
+  // verified folds (with the span fields, single checks only; gbls_fold.h): `fold` marks a source
+  // of the fold call, whether or not it names a group.  Group g sums the signatures of the sets
+  // fold_set[fold_off[g] .. fold_off[g+1]) that verified into fold_out[g] (an affine G2 point),
+  // fold_count[g] and, when asked, fold_bytes[g].  A host source only: the submission that carries
+  // groups runs on one engine.
+  bool fold = false;
+  const uint32_t *fold_set = nullptr;
+  const uint32_t *fold_off = nullptr;
+  size_t nfold = 0;
+  void *fold_out = nullptr;
+  uint8_t (*fold_bytes)[96] = nullptr;
+  uint32_t *fold_count = nullptr;
 };
+
+// Merging callers of the fold call: caller c's groups follow the groups of the callers before it,
+// and its fold_set entries move up by its first set in the merged call.  set/off: the merged CSR
+// (off[0] == 0 written by the caller of this function), gat/eat: the groups and entries merged so
+// far, at: the caller's first set.
+inline void fold_concat(uint32_t *set, uint32_t *off, size_t gat, size_t eat, size_t at, const uint32_t *fold_set,
+                        const uint32_t *fold_off, size_t nfold) {
+  for (size_t g = 1; g <= nfold; g++) off[gat + g] = (uint32_t)(eat + fold_off[g]);
+  const uint32_t cnt = nfold ? fold_off[nfold] : 0;
+  for (uint32_t i = 0; i < cnt; i++) set[eat + i] = (uint32_t)(at + fold_set[i]);
+}
 
 // Merging callers of the local calls: the positions of a caller's LOCAL sets (com[i] ==
 // kLocalSet, gbls_local.h kLocalKeys) move up by the number of local keys of the callers before
@@ -190,10 +213,12 @@ struct Request {
   bool spans() const { return src.cbits != nullptr; }
   // A span source (com, cbits, bits, bits_off; idx and off for its plain sets, off == nullptr
   // when it has none) is a kind of its own whether or not it carries index ranges; a local
-  // source (span | local: a span source with a key table, empty or not) another.
+  // source (span | local: a span source with a key table, empty or not) another, and a fold
+  // source (span | fold: the fold call's requests, with or without groups) one more.
   int kind() const {
     const int sig = (sigs_c ? 4 : 0) | (rands ? 0 : 8);
-    return spans() ? 16 | (src.local ? 32 : 0) | sig : (src.pts ? 1 : 0) | (src.off ? 2 : 0) | sig;
+    return spans() ? 16 | (src.local ? 32 : 0) | (src.fold ? 64 : 0) | sig
+                   : (src.pts ? 1 : 0) | (src.off ? 2 : 0) | sig;
   }
   size_t nkeys() const { return src.off ? src.off[n] : spans() ? 0 : n; }
 };
@@ -222,6 +247,11 @@ struct Config {
 // move up by the local keys before that caller (registry indices stay; gbls_local.h
 // local_rebase), and every caller gets its own slice of the keys' statuses.  Tables that
 // together do not fit 32 bits are not merged: each request then runs on its own.
+// Fold sources: the groups' CSRs are concatenated (fold_concat: each caller's entries move up by
+// its first set, its groups follow the earlier callers'), and every caller gets its own slices of
+// the points, counts and bytes -- only when the merged verification succeeded, so that a failure
+// leaves every caller's fold outputs as its pre-fill wrote them.  Groups or entries that together
+// do not fit 32 bits are not merged either.
 template <class Req, class Verify>
 void run_merged(std::vector<Req *> &batch, Verify &&verify) {
   if (batch.size() == 1) {
@@ -231,7 +261,13 @@ void run_merged(std::vector<Req *> &batch, Verify &&verify) {
   const bool local = batch[0]->src.local;
   uint64_t nloc = 0;
   for (Req *r : batch) nloc += local ? r->src.npkb : 0;
-  if (nloc > 0xffffffffull) {
+  const bool fold = batch[0]->src.fold;
+  uint64_t ngrp = 0, nent = 0;
+  for (Req *r : batch) {
+    ngrp += fold ? r->src.nfold : 0;
+    nent += fold && r->src.nfold ? r->src.fold_off[r->src.nfold] : 0;
+  }
+  if (nloc > 0xffffffffull || ngrp >= 0xffffffffull || nent > 0xffffffffull) {
     for (Req *r : batch) verify(*r);
     return;
   }
@@ -270,7 +306,10 @@ void run_merged(std::vector<Req *> &batch, Verify &&verify) {
   std::vector<uint8_t> pkb(local ? 48 * (size_t)nloc : 0);
   std::vector<int32_t> pst(local ? (size_t)nloc : 0, 1 /* BAD_ENCODING until decoded */);
   std::vector<int32_t> v(nseg, 5 /* VERIFY_FAIL */);
-  size_t at = 0, sat = 0, kat = 0, bat = 0, lat = 0;
+  std::vector<uint32_t> fset((size_t)nent), foff(ngrp ? (size_t)ngrp + 1 : 0, 0), fcnt((size_t)ngrp, 0);
+  std::vector<G2> fpts((size_t)ngrp);
+  std::vector<uint8_t> fbytes(96 * (size_t)ngrp);
+  size_t at = 0, sat = 0, kat = 0, bat = 0, lat = 0, gat = 0, eat = 0;
   seg[0] = 0;
   for (Req *r : batch) {
     std::memcpy(&msgs[32 * at], r->msgs, 32 * r->n);
@@ -302,6 +341,11 @@ void run_merged(std::vector<Req *> &batch, Verify &&verify) {
         local_rebase(idx.data(), off.data(), com.data(), at, r->n, (uint32_t)lat, (uint32_t)r->src.npkb, (uint32_t)nloc);
       lat += r->src.npkb;
     }
+    if (fold && r->src.nfold) {
+      fold_concat(fset.data(), foff.data(), gat, eat, at, r->src.fold_set, r->src.fold_off, r->src.nfold);
+      gat += r->src.nfold;
+      eat += r->src.fold_off[r->src.nfold];
+    }
     for (size_t s = 1; s <= r->nseg; s++) seg[sat + s] = (uint32_t)(at + r->seg_off[s]);
     at += r->n;
     sat += r->nseg;
@@ -331,12 +375,30 @@ void run_merged(std::vector<Req *> &batch, Verify &&verify) {
     m.sigs_c = sigc.data();
     m.sig_status = sst.data();
   }
+  m.src.fold = fold;
+  if (ngrp) {
+    m.src.fold_set = fset.data();
+    m.src.fold_off = foff.data();
+    m.src.nfold = (size_t)ngrp;
+    m.src.fold_out = fpts.data();
+    m.src.fold_bytes = reinterpret_cast<uint8_t(*)[96]>(fbytes.data());
+    m.src.fold_count = fcnt.data();
+  }
   m.prio = r0.prio;
   verify(m);
   sat = 0;
   at = 0;
   lat = 0;
+  gat = 0;
   for (Req *r : batch) {
+    if (fold && r->src.nfold) {
+      if (m.ok) {
+        std::memcpy(r->src.fold_out, &fpts[gat], r->src.nfold * sizeof(G2));
+        std::memcpy(r->src.fold_count, &fcnt[gat], r->src.nfold * 4);
+        if (r->src.fold_bytes) std::memcpy(r->src.fold_bytes, &fbytes[96 * gat], 96 * r->src.nfold);
+      }
+      gat += r->src.nfold;
+    }
     if (local && r->pkb_status && r->src.npkb) std::memcpy(r->pkb_status, &pst[lat], r->src.npkb * 4);
     if (local) lat += r->src.npkb;
     std::memcpy(r->verdicts, &v[sat], r->nseg * 4);

@@ -177,7 +177,7 @@ __global__ void __launch_bounds__(WG) k_aggregate_rows(const aff<F> *pts, uint32
   if (st) st[s] = status;
 }
 // rows for many segments; the 256-lane workgroup form for a few long ones
-constexpr uint32_t kRowAggregateMinSegs = 128;
+// (kRowAggregateMinSegs: gbls_common.h)
 
 // ---------------------------------------------------------------- key material (a15)
 HD void scalar_from_be32(uint32_t (&s)[8], const uint8_t *b) {

@@ -8,12 +8,18 @@ aggregate's sum in ONE `gbls_g2_aggregate_segments` submission (segment k = aggr
 followed by its additions).  A signature that does not decode ends the reference at its first
 use with that addition's bit already set (`?` after `set`), so the mirror keeps exactly the
 bits and sums the reference holds at that point and raises the same DecompressionFailed.
-Rust: rust/bls_patch/sync_committee_pool.rs."""
+Rust: rust/bls_patch/sync_committee_pool.rs.
+
+fold_verified_singles is the host plan of the attestation pool's InsertAttestationTask over
+singular attestations (operation_pools/src/attestation_agg_pool/tasks.rs:183-198, 242-257): the
+singles are verified AND the ones that pass are summed in one engine submission
+(gbls_verify_each_fold), so that no signature is decoded a second time."""
 import ctypes
 from typing import List, Optional, Sequence, Tuple
 
 from . import _lib as G
 from .bls import DecompressionFailed, Signature, decompress_signatures
+from .verifier import MultiVerifier
 
 
 class Aggregate:
@@ -89,3 +95,48 @@ def aggregate_messages(aggregates: List[Aggregate], messages: Sequence[Tuple[Seq
         agg.signature = Signature(raw)
     if first is not None:
         raise DecompressionFailed(dec[plan[first][2]][0])
+
+
+def fold_verified_singles(aggregate: Aggregate, singles: Sequence[Tuple[int, bytes, bytes, int]]):
+    """aggregate_attestation's loop (tasks.rs:189-191, 242-257) over NOT YET VERIFIED singular
+    attestations of one AttestationData, verification and aggregation in ONE engine submission.
+    ``singles`` are (the attester's position in the aggregation bits, the 32-byte signing root, the
+    96-byte signature, the attester's validator index); the registry mirrors those validators.
+
+    Candidates are the first single per position whose bit the aggregate lacks: a single whose bit
+    is already there adds nothing in the reference either (any_not_in is false).  They go up as one
+    group of MultiVerifier.verify_each_fold; afterwards the aggregate's bits gain the positions that
+    verified and its signature gains the group's sum by one addition.  A later single of a position
+    already planned is DEFERRED, not dropped: whether it is needed depends on the first one's
+    verdict, so the caller sends it again if the position is still missing.
+
+    Returns (verified, deferred): per single True / False for a candidate's verdict and None for one
+    that was not sent, and the indices of the deferred singles."""
+    planned, order, deferred = {}, [], []
+    for k, (pos, _, _, _) in enumerate(singles):
+        if aggregate.bits[pos]:
+            continue
+        if pos in planned:
+            deferred.append(k)
+            continue
+        planned[pos] = k
+        order.append(k)
+    verified: List[Optional[bool]] = [None] * len(singles)
+    if not order:
+        return verified, deferred
+    mv = MultiVerifier()
+    for k in order:
+        _, message, signature, index = singles[k]
+        mv.verify_aggregate_indexed(message, signature, [index], (), None)
+    oks, folds = mv.verify_each_fold([list(range(len(order)))])
+    (total, count, _), = folds
+    passed = [k for k, ok in zip(order, oks) if ok]
+    if count != len(passed):
+        raise RuntimeError("the fold's count differs from the verdicts")
+    for k, ok in zip(order, oks):
+        verified[k] = bool(ok)
+    for k in passed:
+        aggregate.bits[singles[k][0]] = True
+    if passed:
+        aggregate.signature = aggregate.signature.aggregate(total)
+    return verified, deferred

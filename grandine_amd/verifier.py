@@ -310,7 +310,9 @@ class MultiVerifier(Verifier):
         self.options = set(options)
         # "local", "spans", "bits", "committees", "indices" or "points": the key form of the last finish (tests)
         self.last_path = None
-        self.last_each_path = None  # "local", "spans" or "points": the key form of the last verify_each / verify_items
+        # "local", "spans" or "points": the key form of the last verify_each / verify_items; "fold": verify_each_fold
+        # with groups
+        self.last_each_path = None
         self.last_each_status = None  # verify_each on "spans": per set (signature status, key status)
 
     @classmethod
@@ -522,6 +524,43 @@ class MultiVerifier(Verifier):
             [t.message for t in self.triples], [t.signature_bytes for t in self.triples],
             [t.keys() for t in self.triples])
         return [status == 0 and ok for status, ok in outcomes]
+
+    def _fold_sets(self):
+        """The triples as the sets of the fold call: finish's "spans" form, or -- singular
+        attestations and sync-committee messages, no committee named at all -- every triple the plain
+        list of its registry indices.  None when they do not qualify."""
+        sets = self._span_sets()
+        if sets is not None:
+            return sets
+        if any(t.key_bytes is not None or t.span_base is not None or t.slot is not None or t.indices is None
+               or not bls.Registry.covers(t.indices) for t in self.triples):
+            return None
+        n = len(self.triples)
+        return [None] * n, [bytes(8)] * n, [b""] * n, [t.indices for t in self.triples]
+
+    def verify_each_fold(self, groups: Iterable[Sequence[int]]):
+        """verify_each which also aggregates what passed (gbls_verify_each_fold): ``groups[g]`` lists
+        triples of this verifier, and the signatures of those that verify on their own are summed on
+        the device, behind the verdicts, in the same submission -- the aggregate_in_place loop of
+        aggregate_attestation (operation_pools/src/attestation_agg_pool/tasks.rs:242-257) without
+        decoding a signature a second time.  Returns (one bool per triple, per group (Signature,
+        count, SignatureBytes)); count == 0: nothing of the group passed, the sum is infinity.
+        Only for triples in the compact forms (finish's "spans" path, or registry indices alone): a
+        fold over key points is not built, and asking for one is an error."""
+        grp = [list(g) for g in groups]
+        if not self.triples:
+            if any(grp):
+                raise ValueError("a group names triples of this verifier")
+            empty = (bls.Signature(), 0, bls.SignatureBytes.empty())
+            return [], [empty for _ in grp]
+        sets = self._fold_sets()
+        if sets is None:
+            raise ValueError("verify_each_fold needs triples in the spans form or over registry indices")
+        self.last_each_path = "fold" if grp else "spans"
+        outcomes, folds = bls.Signature.verify_each_fold(
+            [t.message for t in self.triples], [t.signature_bytes for t in self.triples], *sets, grp)
+        self.last_each_status = [(st, kst) for st, kst, _ in outcomes]
+        return [st == 0 and kst == 0 and ok for st, kst, ok in outcomes], folds
 
     def verify_items(self, item_of_triple: Iterable[int], randoms=None) -> List[bool]:
         """Which ITEMS verify, in ONE device submission (gbls_verify_items_spans): triple k belongs

@@ -27,10 +27,12 @@ pub mod ffi;
 pub mod ffi_bits;
 pub mod ffi_committees;
 pub mod ffi_each;
+pub mod ffi_fold;
 pub mod ffi_local;
 pub mod ffi_msgcache;
 pub mod ffi_msgcache_checks;
 pub mod ffi_spans;
+pub mod fold;
 pub mod local;
 pub mod msgcache;
 pub mod msgcache_checks;

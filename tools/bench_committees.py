@@ -67,11 +67,31 @@ registry entry, decoded inside the submission), three parts:
                     submissions); block is the items call of grandine_bls_gpu_each.h over the block
                     alone, so that the 16 sets' cost shows.
 
+With --fold the call is the verified fold (include/grandine_bls_gpu_fold.h), two shapes of plain
+single-key sets with about 1 % bad signatures, the forms alternating:
+
+  fold          gbls_verify_each_fold: the verdicts and, per group, the sum of the signatures that
+                passed, one submission
+  three         today's best on the same inputs: gbls_verify_each_spans, the host filter of the
+                verdicts (vectorised; its share is reported as three_host_filter_us),
+                gbls_g2_decompress of the passing signatures, each ONCE, their points copied into
+                every segment that names them, gbls_g2_aggregate_segments (three submissions: the
+                yardstick)
+  each          gbls_verify_each_spans alone: what the fold adds to the tail is fold - each
+
+  singles64     64 sets of one message, one group of all
+  subnet2050    2050 sets over four messages (the grouped regime), one group per message and one of
+                all
+
+and after the timed runs one profiled pass of each shape gives the fold stage's device time per
+call (fold_stage_us, the k_g2_fold line of --stages).
+
   python tools/bench_committees.py                       # both shapes, one JSON line per point
   python tools/bench_committees.py --bits                # ... the aggregation-bit leg
   python tools/bench_committees.py --spans               # the span-set leg (its own shape)
   python tools/bench_committees.py --each                # per-set and per-item verdicts (its own shape)
   python tools/bench_committees.py --local               # local key sets (--parts forms,deposits16,block)
+  python tools/bench_committees.py --fold                # verified folds (its own shapes)
   GBLS_COMMITTEE_ROW_MIN=1 python tools/bench_committees.py --tuning --keys-only
 """
 import argparse
@@ -321,6 +341,113 @@ def each_leg(a, G, F, L, emit, absent_counts):
         emit(res)
 
 
+def fold_leg(a, G, F, L, emit):
+    """singles64 and subnet2050: the fold call against the three submissions it replaces and against
+    the each-call alone."""
+    nreg = 4096
+    seed = b"bench-committees/fold"
+    sks, comp = F.registry(nreg, seed)
+    if F.load_registry(comp).any():
+        raise SystemExit("registry load failed")
+    ptr = lambda x: x.ctypes.data_as(ctypes.c_void_p)
+    names = [L.gbls_stage_name(k).decode() for k in range(32) if L.gbls_stage_name(k)]
+    stage = names.index("k_g2_fold")
+    for name, n, nmsg in (("singles64", 64, 1), ("subnet2050", 2050, 4)):
+        um = F.messages(nmsg, seed + name.encode())
+        msgs = b"".join(um[32 * (i % nmsg):32 * (i % nmsg) + 32] for i in range(n))
+        idx = np.ascontiguousarray([(7 * i + 3) % nreg for i in range(n)], dtype=np.uint32)
+        sigs = F.sign([sks[int(v)] for v in idx], msgs)
+        sig_c = ctypes.create_string_buffer(96 * n)
+        G.check(L.gbls_g2_compress(sigs, n, sig_c), "gbls_g2_compress")
+        bad = sorted({(97 * j + 5) % n for j in range(max(1, n // 100))})
+        for i in bad:  # a valid signature of another set
+            j = (i + nmsg) % n
+            sig_c[96 * i:96 * i + 96] = sig_c.raw[96 * j:96 * j + 96]
+        base = np.full(n, G.NO_COMMITTEE, dtype=np.uint32)
+        masks = np.zeros((n, 8), dtype=np.uint8)
+        boff = np.zeros(n + 1, dtype=np.uint32)
+        off = np.arange(n + 1, dtype=np.uint32)
+        groups = ([list(range(n))] if nmsg == 1 else
+                  [list(range(m, n, nmsg)) for m in range(nmsg)] + [list(range(n))])
+        nfold = len(groups)
+        fset = np.ascontiguousarray(np.concatenate(groups), dtype=np.uint32)
+        foff = np.zeros(nfold + 1, dtype=np.uint32)
+        foff[1:] = np.cumsum([len(g) for g in groups])
+        sst, kst, v = G.i32_array(n), G.i32_array(n), G.i32_array(n)
+        out = ctypes.create_string_buffer(192 * nfold)
+        out3 = ctypes.create_string_buffer(192 * nfold)
+        fb = ctypes.create_string_buffer(96 * nfold)
+        cnt = (ctypes.c_uint32 * nfold)()
+        dec = ctypes.create_string_buffer(192 * n)
+        dst, ast = G.i32_array(n), G.i32_array(nfold)
+        want = [int(i not in bad) for i in range(n)]
+        # the host side of the three submissions, vectorised: views on the call's own buffers
+        v_np = np.frombuffer(v, dtype=np.int32, count=n)
+        sig_np = np.frombuffer(sig_c, dtype=np.uint8, count=96 * n).reshape(n, 96)
+        dec_np = np.frombuffer(dec, dtype=np.uint8, count=192 * n).reshape(n, 192)
+        filter_s = []
+
+        def each():
+            return L.gbls_verify_each_spans(msgs, sig_c, ptr(base), ptr(masks), None, ptr(boff), ptr(idx), ptr(off), n,
+                                            sst, kst, v)
+
+        def call(which):
+            t0 = time.perf_counter()
+            if which == "fold":
+                rc = L.gbls_verify_each_fold(msgs, sig_c, ptr(base), ptr(masks), None, ptr(boff), ptr(idx), ptr(off), n,
+                                             ptr(fset), ptr(foff), nfold, sst, kst, v, out, fb, cnt)
+            elif which == "each":
+                rc = each()
+            else:
+                rc = each()
+                if rc == G.SUCCESS:
+                    # the host filter: every passing signature is decoded ONCE, its point then copied
+                    # into every segment that names it
+                    t1 = time.perf_counter()
+                    ok = v_np == G.SUCCESS
+                    passing = np.ascontiguousarray(sig_np[ok])
+                    t2 = time.perf_counter()
+                    rc = L.gbls_g2_decompress(ptr(passing), len(passing), dec, dst)
+                    if rc == G.SUCCESS:
+                        t3 = time.perf_counter()
+                        where = np.cumsum(ok) - 1            # a passing set's place among the decoded points
+                        keep = ok[fset]
+                        pts = np.ascontiguousarray(dec_np[where[fset[keep]]])
+                        o3 = np.concatenate(([0], np.cumsum(keep)))[foff].astype(np.uint32)
+                        t4 = time.perf_counter()
+                        filter_s.append((t2 - t1) + (t4 - t3))
+                        rc = L.gbls_g2_aggregate_segments(ptr(pts), ptr(o3), nfold, out3, ast)
+            dt = time.perf_counter() - t0
+            if rc != G.SUCCESS or [int(v[i] == G.SUCCESS) for i in range(n)] != want:
+                raise SystemExit("%s %s: rc=%d err=%d" % (name, which, rc, L.gbls_last_error()))
+            return dt
+
+        call("fold"), call("three")
+        if out.raw != out3.raw or [cnt[g] for g in range(nfold)] != [sum(want[s] for s in g) for g in groups]:
+            raise SystemExit("%s: the fold and the three submissions disagree" % name)
+        kinds = ["fold", "three", "each"]
+        f, calls = timed(call, kinds, a.warmup, a.window, a.runs)
+        res = {"shape": name, "sets": n, "groups": nfold, "bad": len(bad), "calls_per_run": calls}
+        for kind in kinds:
+            res[kind] = summary(f[kind])
+            res[kind]["runs_us"] = [round(x, 1) for x in f[kind]]
+        res["fold_below_three_range"] = res["fold"]["max_us"] < res["three"]["min_us"]
+        res["added_us"] = round(res["fold"]["median_us"] - res["each"]["median_us"], 1)
+        # the host filter's share of `three` (numpy on views of the call's buffers), inside its timed window
+        res["three_host_filter_us"] = round(statistics.median(filter_s) * 1e6, 1)
+        # the fold stage's device time, one profiled pass
+        ms, ncalls = (ctypes.c_double * 32)(), (ctypes.c_uint32 * 32)()
+        L.gbls_profile(1)
+        L.gbls_profile_reset()
+        for _ in range(20):
+            call("fold")
+        L.gbls_profile_read(ms, ncalls, 32)
+        L.gbls_profile(0)
+        res["fold_stage_us"] = round(1e3 * ms[stage] / max(1, ncalls[stage]), 1)
+        res["fold_stage_calls"] = ncalls[stage]
+        emit(res)
+
+
 def local_leg(a, G, F, L, emit, absent_counts):
     """Local key sets: the decode forms, deposits16 and block8x64x512+16."""
     ptr = lambda x: x.ctypes.data_as(ctypes.c_void_p)
@@ -488,6 +615,9 @@ def main():
                          "without them")
     ap.add_argument("--local", action="store_true",
                     help="the local key set leg: the decode forms, deposits16 and block8x64x512+16")
+    ap.add_argument("--fold", action="store_true",
+                    help="the verified-fold leg: singles64 and subnet2050 through the fold call, the three submissions "
+                         "it replaces and the each-call alone")
     ap.add_argument("--parts", default="", help="with --local: comma-separated parts (forms, deposits16, block)")
     ap.add_argument("--out", default="", help="also append the JSON lines to this file")
     ap.add_argument("--tuning", action="store_true", help="let the engine read its GBLS_* tuning variables")
@@ -513,8 +643,10 @@ def main():
         each_leg(a, G, F, L, emit, [int(x) for x in a.absent.split(",")] if a.absent else [0, 5, 51])
     if a.local:
         local_leg(a, G, F, L, emit, [int(x) for x in a.absent.split(",")] if a.absent else [5])
+    if a.fold:
+        fold_leg(a, G, F, L, emit)
     for name, ncom, size in SHAPES:
-        if a.spans or a.each or a.local or (want and name not in want):
+        if a.spans or a.each or a.local or a.fold or (want and name not in want):
             continue
         nreg = ncom * size
         seed = b"bench-committees/" + name.encode()
