@@ -170,15 +170,17 @@ __device__ __forceinline__ uint32_t repack(const fp &a, uint32_t j) {
   }
   return v;
 }
-// engine Jacobian point -> row form (2 rounds: 6 conversion products)
-__device__ __forceinline__ void load(const Ctx &c, J &o, const g2j &p) {
-  const uint32_t cin = dfp::konst(dfp::K_CIN);
+// engine Jacobian point -> row form (2 rounds: 6 conversion products); cin: the lane's limb of
+// the conversion constant (load28: the slot holds radix-2^28 limbs, bls_curve28.h g2j_store12)
+__device__ __forceinline__ void load(const Ctx &c, J &o, const g2j &p, uint32_t cin) {
   uint32_t v[6] = {repack(p.x.c0, c.t.j), repack(p.x.c1, c.t.j), repack(p.y.c0, c.t.j),
                    repack(p.y.c1, c.t.j), repack(p.z.c0, c.t.j), repack(p.z.c1, c.t.j)};
   mul4(c, o.x.c0, o.x.c1, o.y.c0, o.y.c1, v[0], cin, v[1], cin, v[2], cin, v[3], cin);
   uint32_t d0, d1;
   mul4(c, o.z.c0, o.z.c1, d0, d1, v[4], cin, v[5], cin, v[4], cin, v[5], cin);
 }
+__device__ __forceinline__ void load(const Ctx &c, J &o, const g2j &p) { load(c, o, p, dfp::konst(dfp::K_CIN)); }
+__device__ __forceinline__ void load28(const Ctx &c, J &o, const g2j &p) { load(c, o, p, dfp::konst(dfp::K_CIN28)); }
 __device__ __forceinline__ void load(const Ctx &c, A2 &o, const g2a &p) {
   const uint32_t cin = dfp::konst(dfp::K_CIN);
   mul4(c, o.x.c0, o.x.c1, o.y.c0, o.y.c1, repack(p.x.c0, c.t.j), cin, repack(p.x.c1, c.t.j), cin,

@@ -958,7 +958,7 @@ void set_side_lines(Ctx &c, hipStream_t st, uint32_t nm, bool jac, LineCols lc, 
 // signature (verify / fast_aggregate_verify, signature.rs:51,86).  Streams:
 //   side 1: key resolution (gather / aggregation) -> r_i pk_i
 //   side 2: signature group check, then S = sum r_i sig_i (waits for the keys' flags),
-//           then the lines of the (-g1, S) pairs (or of the MSM's weighted bucket sums)
+//           then the lines of the (-g1, S) pairs (or of the MSM's window sums)
 //   main:   hash_to_G2 -> the sets' lines;  join -> Miller product tree -> partials
 // With message groups (c.plan, GBLS_INIT_DEDUP: msgs holds the U unique messages) the pair space is
 // the U group pairs (sum of the members' r_i pk_i, H(m)) followed by the nseg X extra pairs: the
@@ -1013,8 +1013,7 @@ bool pipeline_partials(Ctx &c, Device &d, const uint8_t *msgs, const uint32_t *m
     mp = msm_plan((uint32_t)n, (uint32_t)nseg);
     if (!c.ensure(c.msm, mp.bytes)) return false;
   }
-  // extra Miller pairs per segment after the n sets: (-g1, S), or the MSM's weighted
-  // bucket / window sums
+  // extra Miller pairs per segment after the n sets: (-g1, S), or the MSM's window sums
   const size_t X = msm ? mp.extra : 1;
   const size_t np = nq + nseg * X;
   // ---- host tables, one staged upload:
@@ -1127,9 +1126,12 @@ bool pipeline_partials(Ctx &c, Device &d, const uint8_t *msgs, const uint32_t *m
             mcp ? " (line cache)" : "");
   // latency regime: each segment's S = sum r_i sig_i stays Jacobian (no inversion), its lines
   // taken projectively (k_lines_w4j)
+  // (with the c = 5 bucket MSM: its nseg X window sums, k_msm_windows_w4; the lines_s_main
+  // experiment takes them affine, as event-sliced submissions and those of more windows do)
   g2j *sj = nullptr;
-  if (!msm && !single && !sliced && X == 1 && nseg <= kW4Max) {
-    if (!c.ensure(c.Sj, nseg * sizeof(g2j) + 16)) return false;
+  const bool msm_jac = msm && !mp.tree && !g.lines_s_main;
+  if ((msm ? msm_jac : !single && X == 1) && !sliced && nseg * X <= kW4Max) {
+    if (!c.ensure(c.Sj, nseg * X * sizeof(g2j) + 16)) return false;
     sj = c.Sj.as<g2j>();
   }
   const uint32_t *T = c.tab.as<uint32_t>();
@@ -1181,7 +1183,7 @@ bool pipeline_partials(Ctx &c, Device &d, const uint8_t *msgs, const uint32_t *m
     HIPCHK(hipStreamWaitEvent(side2, c.ev_pks, 0));
     StageTimer t(S_MSM, side2);
     launch_msm(side2, mp, c.msm.as<uint8_t>(), sigs, rands, pks, pre, pre2, N, T + segoff_at,
-               empty_is_error, c.H.as<g2a>(), c.P.as<g1s>(), seg_err, NQ);
+               empty_is_error, c.H.as<g2a>(), c.P.as<g1s>(), seg_err, NQ, sj);
   } else if (!single) {
     StageTimer t(S_G2MUL, side2);
     launch_mv_g2mul(side2, sigs, rands, N, c.R.as<g2j>());
@@ -1205,7 +1207,7 @@ bool pipeline_partials(Ctx &c, Device &d, const uint8_t *msgs, const uint32_t *m
   const bool lines_s_main = msm && !sliced && g.lines_s_main;
   if (!lines_s_main) {  // the extra pairs' lines of the first event slice (all events when not sliced)
     StageTimer t(S_LINES_S, side2);
-    if (!sj || !launch_lines_jac(side2, sj, 1, NQ, NS, lc, c.lines.as<uint32_t>()))
+    if (!sj || !launch_lines_jac(side2, sj, 1, NQ, (uint32_t)(nseg * X), lc, c.lines.as<uint32_t>()))
       launch_lines(side2, c.H.as<g2a>(), NQ, (uint32_t)(nseg * X), lc, 0, EC, c.Ts.as<g2h>(),
                    c.lines.as<uint32_t>(), g.lines_s_lane);
   }

@@ -182,8 +182,8 @@ struct MsmPlan {
   uint32_t max_chunks;  // bound on the chunk count (grid of the chunk kernel)
   uint32_t K;           // points per chunk
   uint32_t max_folds;   // bound on the level-0 fold-pair count (grid of the fold kernels)
-  bool tree;            // per-window bucket trees (c = 13) or per-bucket pairs (c = 5)
-  uint32_t extra;       // extra Miller pairs per segment: W (tree) or W * 2^(c-1)
+  bool tree;            // per-window bucket trees (c = 13) or per-window wave sums (c = 5)
+  uint32_t extra;       // extra Miller pairs per segment: W, one per window
   bool r28;             // chunk sums and folds in radix 2^28 (g_msm_r28)
   size_t o_cnt, o_start, o_cur, o_cstart, o_fstart[kMsmFoldLevels], o_list, o_chunk, o_t0, o_a0, o_t1, o_a1,
       o_sig28, bytes;
@@ -196,13 +196,14 @@ struct MsmPlan {
 constexpr uint32_t kMsmMinPerSeg = 2048;
 MsmPlan msm_plan(uint32_t n, uint32_t nseg);
 // writes each segment's p.extra Miller pairs (P[xbase + s * extra + k] = a constant G1 weight,
-// H[...] = affine bucket or window sum; xbase = NONE: n), zeroes seg_err and flags empty segments
-// when empty_is_error
+// H[...] = affine window sum; xbase = NONE: n), zeroes seg_err and flags empty segments
+// when empty_is_error.  Sj (c = 5 only): the window sums stay Jacobian, Sj[s * extra + k], for
+// launch_lines_jac, and H is not written
 // (pks, pre, pre2: the segment error flags of k_msm_count, as k_g2sum_final sets them)
 void launch_msm(hipStream_t st, const MsmPlan &p, uint8_t *ws, const g2a *sigs,
                 const uint64_t *rands, const g1a *pks, const int32_t *pre, const int32_t *pre2,
                 uint32_t n, const uint32_t *seg_off, int empty_is_error, g2a *H, g1s *P,
-                int32_t *seg_err, uint32_t xbase = NONE);
+                int32_t *seg_err, uint32_t xbase = NONE, g2j *Sj = nullptr);
 
 // k_lines.hip -- Miller-loop line functions of every pair
 // Where a pair's lines live: column col[pair] of ncol (col null: column = pair); word w of

@@ -520,32 +520,42 @@ void launch_ml_pcols(hipStream_t st, const g1s *P, const uint32_t *col, uint32_t
   else
     k_ml_pcols<false><<<nblk(np), WG, 0, st>>>(P, col, np, ncol, Pc);
 }
+// launches of up to this many blocks (1.5 per SIMD of the 1024) run in event-major order
+constexpr uint32_t kMlXcdMinBlocks = 1536;
 void launch_ml_group(hipStream_t st, const uint32_t *lines, LineCols lc, uint32_t ngp, const g1s *P,
                      const uint32_t *Pc, const uint32_t *plist, const uint32_t *groups, uint32_t ngroup, int e0,
                      int e1, fp12 *V0, uint32_t *V28, bool pcn) {
   dim3 grid(nblk(ngroup), e1 - e0);
   if (!ngroup || e1 <= e0) return;
   const dim3 grid1(nblk(ngroup) * (uint32_t)(e1 - e0));
+  // XCD order pays where the launch is large enough for the G1 points' re-reads to matter (C2's
+  // 16-batch launch: 2040 blocks).  A launch of about one block per SIMD gains nothing from it and
+  // loses when its last group block is ragged: the XCD order puts that block's ne nearly empty
+  // waves on one XCD as the last work dispatched.  Measured at 17 x 68 = 1156 blocks (one 4096-set
+  // batch): 0.31 ms with 52 live lanes in the last group block (1076 groups), 0.36 / 0.50 / 0.50 ms
+  // with 16 / 8 / 4 (1040 / 1032 / 1028 groups), 0.31 ms in event-major order at 1028
+  // (DESIGN.md section 21).  Such launches keep the event-major order.
+  const int xcd = g_ml_xcd && grid1.x > kMlXcdMinBlocks ? (int)g_ml_xcd : 0;
   if (g_ml_r28 && V28) {
     if (g_ml_dma)
-      k_ml_group28<true, false><<<grid1, WG, 0, st>>>(lines, lc, ngp, P, Pc, plist, groups, ngroup, e0, e1 - e0, (int)g_ml_xcd, V28);
+      k_ml_group28<true, false><<<grid1, WG, 0, st>>>(lines, lc, ngp, P, Pc, plist, groups, ngroup, e0, e1 - e0, xcd, V28);
     else if (g_ml_kara && pcn)
-      k_ml_group28<false, false, true, true><<<grid1, WG, 0, st>>>(lines, lc, ngp, P, Pc, plist, groups, ngroup, e0, e1 - e0, (int)g_ml_xcd, V28);
+      k_ml_group28<false, false, true, true><<<grid1, WG, 0, st>>>(lines, lc, ngp, P, Pc, plist, groups, ngroup, e0, e1 - e0, xcd, V28);
     else if (g_ml_kara)
-      k_ml_group28<false, false, true><<<grid1, WG, 0, st>>>(lines, lc, ngp, P, Pc, plist, groups, ngroup, e0, e1 - e0, (int)g_ml_xcd, V28);
+      k_ml_group28<false, false, true><<<grid1, WG, 0, st>>>(lines, lc, ngp, P, Pc, plist, groups, ngroup, e0, e1 - e0, xcd, V28);
     else if (g_ml_prefetch && pcn)  // the points by column, normalized (k_ml_pcols): 4-product lines
-      k_ml_group28<false, true, false, true><<<grid1, WG, 0, st>>>(lines, lc, ngp, P, Pc, plist, groups, ngroup, e0, e1 - e0, (int)g_ml_xcd, V28);
+      k_ml_group28<false, true, false, true><<<grid1, WG, 0, st>>>(lines, lc, ngp, P, Pc, plist, groups, ngroup, e0, e1 - e0, xcd, V28);
     else if (g_ml_prefetch)
-      k_ml_group28<false, true><<<grid1, WG, 0, st>>>(lines, lc, ngp, P, Pc, plist, groups, ngroup, e0, e1 - e0, (int)g_ml_xcd, V28);
+      k_ml_group28<false, true><<<grid1, WG, 0, st>>>(lines, lc, ngp, P, Pc, plist, groups, ngroup, e0, e1 - e0, xcd, V28);
     else if (pcn)
-      k_ml_group28<false, false, false, true><<<grid1, WG, 0, st>>>(lines, lc, ngp, P, Pc, plist, groups, ngroup, e0, e1 - e0, (int)g_ml_xcd, V28);
+      k_ml_group28<false, false, false, true><<<grid1, WG, 0, st>>>(lines, lc, ngp, P, Pc, plist, groups, ngroup, e0, e1 - e0, xcd, V28);
     else
-      k_ml_group28<false, false><<<grid1, WG, 0, st>>>(lines, lc, ngp, P, Pc, plist, groups, ngroup, e0, e1 - e0, (int)g_ml_xcd, V28);
+      k_ml_group28<false, false><<<grid1, WG, 0, st>>>(lines, lc, ngp, P, Pc, plist, groups, ngroup, e0, e1 - e0, xcd, V28);
     const uint32_t nvals = ngroup * (uint32_t)(e1 - e0);
     k_ml_pack28<<<nblk((size_t)nvals * 12), WG, 0, st>>>(V28, ngroup, e0, nvals, V0);
     return;
   }
-  k_ml_group<<<grid1, WG, 0, st>>>(lines, lc, ngp, P, plist, groups, ngroup, e0, e1 - e0, (int)g_ml_xcd, V0);
+  k_ml_group<<<grid1, WG, 0, st>>>(lines, lc, ngp, P, plist, groups, ngroup, e0, e1 - e0, xcd, V0);
 }
 void launch_ml_reduce(hipStream_t st, const fp12 *Vin, uint32_t nin, const uint32_t *red,
                       uint32_t nout, fp12 *Vout) {

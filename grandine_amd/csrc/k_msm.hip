@@ -16,38 +16,41 @@
 //   4b k_msm_fold    kMsmFoldLevels launches, lane per pair of one bucket's partials at
 //                    level l: partial[j] += partial[j + 2^l] (full Jacobian additions), so
 //                    each run of kMsmFold partials ends summed in its first; the bucket's
-//                    reader adds the runs' sums (msm_bucket_sum)
+//                    reader adds the runs' sums (k_msm_windows_w4, msm_bucket_sum)
 // (r05: the chunk kernel no longer folds its wave's partials through LDS -- log2(run) levels
 // of additions at whole-wave cost with most lanes masked off; the fold levels are their own
 // launches, every lane one addition, so K can be small: GBLS_MSM_K = 8 gives ~1.7k chunk
 // waves against 884 at K = 16, VERDICT r04 item 4, at the same C2 rate)
-// The bucket sums X_{w,b} never go through a Horner chain of 60 doublings.  The weights
-// move to the G1 side of the pairing instead, where they are constants:
-//   e(-g1, S) = prod_{w,b} e(-[(b+1) 2^(c w)] g1, X_{w,b}),
-// so every bucket becomes one extra Miller pair of its segment, with a precomputed G1
-// point (bls_constants.h MSM_W5, tools/gen_constants.py).  With c = 5 that is
-// 13 * 16 = 208 pairs per segment (+5% Miller work at 4096 sets), and the G2 side has
-// no serial tail:
-//   5 k_msm_pairs    lane per bucket: X_{w,b} (the bucket's partials), affine, its pair
+// The window sums never go through a Horner chain of 60 doublings.  The window weights move
+// to the G1 side of the pairing instead, where they are constants:
+//   e(-g1, S) = prod_w e(-[2^(c w)] g1, S_w),   S_w = sum_b (b + 1) X_{w,b},
+// so every window becomes one extra Miller pair of its segment, with a precomputed G1 point
+// (bls_constants.h MSM_W5 entry 16 w / MSM_W13 entry w, tools/gen_constants.py).  With c = 5
+// that is 13 pairs per segment, and the bucket weights (b + 1) are folded on the wave engine:
+//   5 k_msm_windows_w4  (k_msm_w4.hip) workgroup per (segment, window): the buckets' partials
+//                    added up and S_w by running sums, Jacobian for k_lines_w4j (or affine)
+// (until r06 every bucket sum was a pair of its own, paired with -[(b+1) 2^(c w)] g1: 208
+// pairs per segment whose lines ran 16 lanes per point on the whole GPU)
 // With c = 13 (segments >= 2^16 sets, 4096 buckets per window) a per-window tree
-// first folds the weights (b + 1) into S_w, and the 5 window sums pair with
-// -[2^(13 w)] g1 (MSM_W13):
+// folds the weights (b + 1) into S_w:
 //   5 k_msm_bucket   level-0 tree nodes (the buckets' partials added up)
 //   6 k_msm_tree     per (segment, window), a binary tree over the buckets computing
 //                    S_w = sum_b (b+1) X_b with nodes (T = sum X, A = sum (b - lo) X):
 //                    T = T_L + T_R, A = A_L + A_R + 2^l T_R   (l = level)
 //   7 k_msm_wpairs   lane per window: affine S_w = A + T, its pair
 // Infinite signatures and zero scalars contribute nothing (blst skips infinite
-// signatures; a zero scalar fails the batch through k_msm_count's flags).  An empty bucket is
-// the point at infinity, whose Miller pair is the identity.  Bucket order is
+// signatures; a zero scalar fails the batch through k_msm_count's flags).  An empty window sums
+// to the point at infinity, whose Miller pair is the identity.  Bucket order is
 // nondeterministic (atomics) but the sums are exact, so the verdict is too.
 //
 // r06: the chunk sums and the fold levels run in radix 2^28 (k_msm_chunk28 / k_msm_fold28,
 // bls_curve28.h's lazy jac_add_aff28 / jac_add28): k_msm_count writes each scattered
 // signature once in radix 2^28 (4 conversion products per set, against ~13 additions of it),
 // partials are stored as radix-2^28 limbs in the engine layout (store12), and the bucket
-// readers (k_msm_pairs / k_msm_bucket) convert their sums back to engine form.
+// readers convert them: k_msm_windows_w4 straight to the wave engine's row form (w4::load28),
+// k_msm_bucket back to engine form.
 #include "gbls_common.h"
+#include "k_msm.h"
 #include "bls_gang.h"
 #include "bls_curve28.h"
 
@@ -313,37 +316,6 @@ __device__ __forceinline__ void msm_bucket_sum(g2j &x, const g2j *chunk, const u
   }
 }
 
-// the constant G1 half of an extra pair: table entry k (x, y Montgomery), c = 1
-__device__ __forceinline__ void msm_weight(g1s &o, const uint32_t *table, uint32_t k) {
-#pragma unroll
-  for (int i = 0; i < 12; i++) {
-    o.x.l[i] = table[24 * k + i];
-    o.y.l[i] = table[24 * k + 12 + i];
-  }
-  fp_one(o.c);
-}
-
-// c = 5: lane per bucket t = s * W * B + k; its sum X (the bucket's folded first chunk, or
-// infinity) pairs with -[(b+1) 2^(c w)] g1 at pair n + t
-template <bool R28>
-__global__ void __launch_bounds__(WG) k_msm_pairs(const g2j *chunk, const uint32_t *cstart,
-                                                  uint32_t nb, uint32_t per_seg, uint32_t n,
-                                                  const uint32_t *seg_off, int empty_is_error,
-                                                  g1s *P, g2a *H, int32_t *seg_err) {
-  uint32_t t = blockIdx.x * WG + threadIdx.x;
-  if (t >= nb) return;
-  uint32_t s = t / per_seg, k = t % per_seg;
-  g2j x;
-  msm_bucket_sum<R28>(x, chunk, cstart, t);
-  g2a a;
-  jac_to_aff(a, x);
-  g1s w;
-  msm_weight(w, k::MSM_W5, k);
-  P[n + t] = w;
-  H[n + t] = a;
-  if (k == 0 && empty_is_error && seg_off[s + 1] == seg_off[s]) atomicOr(&seg_err[s], 1);
-}
-
 // level-0 tree nodes: T = X_b (the bucket's folded first chunk, or infinity), A = inf
 template <bool R28>
 __global__ void __launch_bounds__(WG) k_msm_bucket(const g2j *chunk, const uint32_t *cstart,
@@ -399,8 +371,8 @@ __global__ void __launch_bounds__(WG) k_msm_wpairs(const g2j *T, const g2j *A, u
 // ---------------------------------------------------------------- host side
 // Window widths dividing 65 (64-bit scalars + the signed-digit carry), so that no window
 // is nearly empty (a 2-bit top window would pile every set into two buckets): c = 5
-// (13 windows, 16 buckets each, one Miller pair per bucket) for segments up to 2^16 sets,
-// else c = 13 (5 windows of 4096 buckets, per-window trees, one pair per window).
+// (13 windows, 16 buckets each, summed per window on the wave engine) for segments up to 2^16
+// sets, else c = 13 (5 windows of 4096 buckets, per-window trees); one pair per window.
 MsmPlan msm_plan(uint32_t n, uint32_t nseg) {
   uint32_t avg = nseg ? n / nseg : n;
   MsmPlan p;
@@ -408,7 +380,7 @@ MsmPlan msm_plan(uint32_t n, uint32_t nseg) {
   p.c = avg >= (1u << 16) ? 13 : 5;
   p.W = 65 / p.c;
   p.tree = p.c == 13;
-  p.extra = p.tree ? (uint32_t)p.W : ((uint32_t)p.W << (p.c - 1));
+  p.extra = (uint32_t)p.W;
   p.nb = nseg * ((uint32_t)p.W << (p.c - 1));
   // chunks of <= K points (GBLS_MSM_K; else kMsmChunkSmall below 4096 sets per segment,
   // kMsmChunk from there), fold groups of kMsmFold chunk partials
@@ -442,7 +414,7 @@ MsmPlan msm_plan(uint32_t n, uint32_t nseg) {
 void launch_msm(hipStream_t st, const MsmPlan &p, uint8_t *ws, const g2a *sigs,
                 const uint64_t *rands, const g1a *pks, const int32_t *pre, const int32_t *pre2,
                 uint32_t n, const uint32_t *seg_off, int empty_is_error, g2a *H, g1s *P,
-                int32_t *seg_err, uint32_t xbase) {
+                int32_t *seg_err, uint32_t xbase, g2j *Sj) {
   // the pair kernels' `n` is only the index of the first extra pair
   const uint32_t xb = xbase == NONE ? n : xbase;
   uint32_t *cnt = reinterpret_cast<uint32_t *>(ws + p.o_cnt);
@@ -475,12 +447,8 @@ void launch_msm(hipStream_t st, const MsmPlan &p, uint8_t *ws, const g2a *sigs,
       k_msm_fold<<<nblk(mp), WG, 0, st>>>(cstart, fs.l[l], p.nb, mp, l, chunk);
   }
   if (!p.tree) {
-    if (p.r28)
-      k_msm_pairs<true><<<nblk(p.nb), WG, 0, st>>>(chunk, cstart, p.nb, p.extra, xb, seg_off,
-                                                   empty_is_error, P, H, seg_err);
-    else
-      k_msm_pairs<false><<<nblk(p.nb), WG, 0, st>>>(chunk, cstart, p.nb, p.extra, xb, seg_off,
-                                                    empty_is_error, P, H, seg_err);
+    launch_msm_windows_w4(st, chunk, cstart, p.nseg * (uint32_t)p.W, (uint32_t)p.W, p.r28, xb, seg_off,
+                          empty_is_error, P, H, seg_err, Sj);
     return;
   }
   g2j *T[2] = {reinterpret_cast<g2j *>(ws + p.o_t0), reinterpret_cast<g2j *>(ws + p.o_t1)};

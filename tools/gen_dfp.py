@@ -280,6 +280,8 @@ def main():
         "CIN": limbs(pow(2, 2 * N * W - 384, P)),   # engine form (x 2^384) -> x 2^448
         "COUT": limbs(pow(2, 384, P)),              # x 2^448 -> x 2^384
         "ONE": limbs(mont(1)),
+        # radix-2^28 limbs kept in an engine-layout slot (bls_curve28.h store12: x 2^392) -> x 2^448
+        "CIN28": limbs(pow(2, 2 * N * W - 392, P)),
         # subtraction biases: R1 of the Fp12 product subtracts <= 6 products (< 1.0001 p,
         # limbs < 2^28 + 2^9); R2 <= 2 R1 values (< 14.001 p, limbs < 2^28 + 16); NEG negates
         # one coefficient (< 128 p, limbs < 2^28 + 2^9)
