@@ -447,4 +447,22 @@ __device__ __forceinline__ void to_words_all(uint32_t (&w)[12], uint32_t x, cons
 }
 
 }  // namespace dfp
+
+// The (p-3)/4 exponentiation policy of the row kernels (k_h2c_map_row, k_g2_decompress_row;
+// tools/ubench/h2c_check.hip runs the same struct): every lane of a 16-lane row holds the same
+// engine-form element (F: 12 words in .l), the row raises it to (p-3)/4 and every lane gets the
+// canonical words back.
+struct RowPow {
+  template <class F>
+  __device__ void operator()(F &r, const F &a) const {
+    dfp::Tabs t;
+    dfp::load_tabs(t);
+#if defined(GBLS_MAP_NOPOW)  // timing experiment (wrong points)
+    const uint32_t x = dfp::from_regs(a.l, t);
+#else
+    const uint32_t x = dfp::pow_pm3d4(dfp::from_regs(a.l, t), t);
+#endif
+    dfp::to_words_all(r.l, x, t);
+  }
+};
 }  // namespace gbls

@@ -45,15 +45,7 @@ __global__ void __launch_bounds__(WG) k_g2_decompress(const uint8_t *in, uint32_
 
 // one 16-lane row per signature (the latency regime: blocks' MultiVerifier::finish): the two
 // (p-3)/4 exponentiations of the Fp2 square root row-distributed (bls_dfp.h), ~2.5x faster
-// per product than one lane's; the rest of the decoding runs redundantly on the row's lanes
-struct RowPowDec {
-  __device__ void operator()(fp &r, const fp &a) const {
-    dfp::Tabs t;
-    dfp::load_tabs(t);
-    const uint32_t x = dfp::pow_pm3d4(dfp::from_regs(a.l, t), t);
-    dfp::to_words_all(r.l, x, t);
-  }
-};
+// per product than one lane's (RowPow); the rest of the decoding runs redundantly on the row's lanes
 template <bool X>
 __global__ void __launch_bounds__(WG) k_g2_decompress_row(const uint8_t *in, uint32_t n, g2a *out,
                                                           int32_t *st) {
@@ -61,7 +53,7 @@ __global__ void __launch_bounds__(WG) k_g2_decompress_row(const uint8_t *in, uin
   const uint32_t i = (blockIdx.x * WG + threadIdx.x) >> 4;
   if (i >= n) return;  // whole rows
   g2a a;
-  int32_t s = g2_decompress_pow(a, in + 96u * i, RowPowDec());
+  int32_t s = g2_decompress_pow(a, in + 96u * i, RowPow());
   if (s != ST_SUCCESS) {
     fp2_zero(a.x);
     fp2_zero(a.y);

@@ -18,19 +18,7 @@ __global__ void __launch_bounds__(WG) k_h2c_map(const fp2 *U, uint32_t nu, g2j *
 // The two (p-3)/4 exponentiations of a map on the element's 16-lane row (bls_dfp.h): every
 // lane of the row runs the per-lane map code redundantly on the same data, and the
 // exponentiations -- 2 x 458 dependent products, most of the map's latency -- run
-// row-distributed, ~2.5x faster per product than one lane's.
-struct RowPow {
-  __device__ void operator()(fp &r, const fp &a) const {
-    dfp::Tabs t;
-    dfp::load_tabs(t);
-#if defined(GBLS_MAP_NOPOW)  // timing experiment (wrong points)
-    const uint32_t x = dfp::from_regs(a.l, t);
-#else
-    const uint32_t x = dfp::pow_pm3d4(dfp::from_regs(a.l, t), t);
-#endif
-    dfp::to_words_all(r.l, x, t);
-  }
-};
+// row-distributed, ~2.5x faster per product than one lane's (RowPow, bls_dfp.h).
 template <bool X>
 __global__ void __launch_bounds__(WG) k_h2c_map_row(const fp2 *U, uint32_t nu, g2j *Q) {
   if constexpr (X) w4::exclusive_simd();

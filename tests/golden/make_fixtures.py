@@ -318,7 +318,228 @@ def main():
         with open(os.path.join(HERE, "trusted_setup.bin"), "wb") as fh:
             fh.write(n1.to_bytes(4, "little") + n2.to_bytes(4, "little") + g1 + g2)
     print("fixtures written:", sorted(out))
+    edges_main()
+
+
+# ------------------------------------------------------------------------------------------------
+# small_order.json / decode_edges.json: inputs an untrusted peer can send (tests/test_gpu_edges.py).
+# Own seed and own files, so the fixtures above stay byte-identical.
+#   python tests/golden/make_fixtures.py edges     regenerates these two files only
+# ------------------------------------------------------------------------------------------------
+H1 = (O.X - 1) ** 2 // 3  # cofactor of G1 in E1(Fp)
+H2 = (O.X ** 8 - 4 * O.X ** 7 + 5 * O.X ** 6 - 4 * O.X ** 4 + 6 * O.X ** 3 - 4 * O.X ** 2 - 4 * O.X + 13) // 9
+E2_ORDERS = (13, 23, 2713, 11953)
+E1_ORDERS = (11, 10177, 859267)
+
+
+def random_e1(rng):
+    while True:
+        x = rng.randrange(O.P)
+        y = O.fp_sqrt(x * x * x + 4)
+        if y is not None:
+            return (x, y)
+
+
+def random_e2(rng):
+    while True:
+        x = (rng.randrange(O.P), rng.randrange(O.P))
+        y = O.f2_sqrt(O.f2_add(O.f2_mul(O.f2_sqr(x), x), O.B2))
+        if y is not None:
+            return (x, y)
+
+
+def point_of_order(q, h, mul, rand, rng):
+    """A point of exact order q: T = [n / q^e] S with q^e the full power of q in h (the q-torsion
+    may be fully rational, so [n / q] S alone is always infinity there), then [q] until [q]T = O."""
+    qe = 1
+    while h % (qe * q) == 0:
+        qe *= q
+    assert qe > 1
+    while True:
+        t = mul(rand(rng), h * O.R // qe)
+        if t is None:
+            continue
+        while mul(t, q) is not None:
+            t = mul(t, q)
+        return t
+
+
+def f2hex(a):
+    return ["%096x" % a[0], "%096x" % a[1]]
+
+
+def g2rec(pt):
+    return {"enc": O.g2_compress(pt).hex(), "x": f2hex(pt[0]), "y": f2hex(pt[1])}
+
+
+def g1rec(pt):
+    return {"enc": O.g1_compress(pt).hex(), "x": "%096x" % pt[0], "y": "%096x" % pt[1]}
+
+
+def g2_edge_x(rng, kind):
+    """x with Im(x^3 + B2) = 0 (kind "im0": y^2 lies in Fp, so y is real or purely imaginary)
+    or Re(x^3 + B2) = 0 (kind "re0": y^2 is purely imaginary)."""
+    while True:
+        if kind == "im0":
+            x1 = rng.randrange(1, O.P)
+            x0 = O.fp_sqrt((x1 ** 3 - 4) * O.fp_inv(3 * x1))
+            if x0 is None:
+                continue
+        else:
+            x0 = rng.randrange(1, O.P)
+            x1 = O.fp_sqrt((x0 ** 3 + 4) * O.fp_inv(3 * x0))
+            if x1 is None:
+                continue
+        x = (x0, x1)
+        a = O.f2_add(O.f2_mul(O.f2_sqr(x), x), O.B2)
+        assert a[1 if kind == "im0" else 0] == 0
+        return x, a
+
+
+def edges_main():
+    rng = random.Random(20261021)
+    assert O.g1_mul(random_e1(rng), H1 * O.R) is None and O.g2_mul(random_e2(rng), H2 * O.R) is None
+
+    # -- points of small order ---------------------------------------------------------------
+    e2 = []
+    for q in E2_ORDERS:
+        t = point_of_order(q, H2, O.g2_mul, random_e2, rng)
+        assert O.g2_on_curve(t) and O.g2_mul(t, q) is None and not O.g2_in_group(t)
+        e2.append({"order": q, "T": g2rec(t), "negT": g2rec(O.g2_neg(t)), "T_plus_gen": g2rec(O.g2_add(t, O.G2_GEN))})
+    e1 = []
+    for q in E1_ORDERS:
+        t = point_of_order(q, H1, O.g1_mul, random_e1, rng)
+        assert O.g1_on_curve(t) and O.g1_mul(t, q) is None and not O.g1_in_group(t)
+        e1.append({"order": q, "T": g1rec(t), "T_plus_gen": g1rec(O.g1_add(t, O.G1_GEN))})
+    small = {"provenance": "oracle: T = [h r / q^e] S for seeded random S, times q until [q]T = O; none is in its "
+                           "prime-order subgroup ([r]P != O)", "e2": e2, "e1": e1}
+
+    # -- G2 decoding: roots that lie in Fp or in u Fp --------------------------------------------
+    roots = []
+    count = {"real": 0, "imag": 0, "re0": 0}
+    while min(count["real"], count["imag"]) < 4:
+        x, a = g2_edge_x(rng, "im0")
+        y = O.f2_sqrt(a)
+        cls = "real" if y[1] == 0 else "imag"
+        assert y[0 if cls == "imag" else 1] == 0 and (cls == "imag") == (not O.fp_is_square(a[0]))
+        if count[cls] >= 5:
+            continue
+        count[cls] += 1
+        roots.append((cls, x, y))
+    while count["re0"] < 2:
+        x, a = g2_edge_x(rng, "re0")
+        y = O.f2_sqrt(a)
+        assert y is not None and y[0] != 0 and y[1] != 0
+        count["re0"] += 1
+        roots.append(("re0", x, y))
+    rcases = []
+    for cls, x, y in roots:
+        for yy in (y, O.f2_neg(y)):
+            enc = O.g2_compress((x, yy))
+            st, pt = O.g2_decompress(enc)
+            assert st == O.SUCCESS and pt == (x, yy)
+            rcases.append({"class": cls, "in": enc.hex(), "status": st, "x": f2hex(x), "y": f2hex(yy),
+                           "in_group": O.g2_in_group(pt)})
+
+    # -- G2 flag and range edges ------------------------------------------------------------------
+    valid = O.g2_compress(O.g2_mul(O.G2_GEN, 0x1234567))
+    p48 = O.P.to_bytes(48, "big")
+
+    def enc2(c1, c0, flags=0x80):
+        b = bytearray(c1.to_bytes(48, "big") + c0.to_bytes(48, "big"))
+        b[0] |= flags
+        return bytes(b)
+
+    def on_curve_c0(c1, start):
+        """A c0 >= start that puts (c0, c1) on the curve."""
+        c0 = start
+        while O.g2_decompress(enc2(c1, c0))[0] != O.SUCCESS:
+            c0 += 1
+        return c0
+
+    def on_curve_c1(c0, start):
+        c1 = start
+        while O.g2_decompress(enc2(c1, c0))[0] != O.SUCCESS:
+            c1 += 1
+        return c1
+
+    vc1 = int.from_bytes(bytes([valid[0] & 0x1F]) + valid[1:48], "big")
+    fl = [
+        ("0xe0 then zeros", bytes([0xE0]) + bytes(95)),
+        ("infinity, non-zero byte in the second half", bytes([0xC0]) + bytes(69) + b"\x01" + bytes(25)),
+        ("infinity, non-zero last byte of the first half", bytes([0xC0]) + bytes(46) + b"\x01" + bytes(48)),
+        ("compression bit clear on a valid point", bytes([valid[0] & 0x7F]) + valid[1:]),
+        ("valid point", valid),
+        ("x.c1 = p-1, on the curve", enc2(O.P - 1, on_curve_c0(O.P - 1, 0))),
+        ("x.c1 = p-1, sign bit", enc2(O.P - 1, on_curve_c0(O.P - 1, 0), 0xA0)),
+        ("x.c0 = p-1, on the curve", enc2(on_curve_c1(O.P - 1, 1), O.P - 1)),
+        ("x.c1 = p-1, x.c0 = p-1", enc2(O.P - 1, O.P - 1)),
+        ("x.c0 = p, valid c1", valid[:48] + p48),
+        ("x.c0 = p+1, valid c1", valid[:48] + (O.P + 1).to_bytes(48, "big")),
+        ("x.c0 = 2^384-1, valid c1", valid[:48] + b"\xff" * 48),
+        ("x.c1 = p", enc2(O.P, 5)),
+        ("x.c1 >= p in its top bits only: 0x1b then zeros", bytes([0x80 | 0x1B]) + bytes(95)),
+        ("x.c1 >= p in its top bits only: valid c1 with its five top bits set", enc2(vc1 | 0x1F << 376, 7)),
+        ("x.c1 = 2^381-1", bytes([0x9F]) + b"\xff" * 47 + bytes(48)),
+        ("x = 0", enc2(0, 0)),
+        ("x = 0, sign bit", enc2(0, 0, 0xA0)),
+        ("all 0xff", b"\xff" * 96),
+        ("infinity with the sign bit and a low x bit", bytes([0xE0]) + bytes(94) + b"\x01"),
+    ]
+    fcases = []
+    for note, b in fl:
+        st, pt = O.g2_decompress(b)
+        rec = {"note": note, "in": b.hex(), "status": st}
+        if st == O.SUCCESS and pt is not None:
+            rec.update({"x": f2hex(pt[0]), "y": f2hex(pt[1]), "in_group": O.g2_in_group(pt)})
+        elif st == O.SUCCESS:
+            rec.update({"x": None, "y": None, "in_group": True})
+        fcases.append(rec)
+
+    # -- G1 range edges -----------------------------------------------------------------------------
+    def enc1(x, flags=0x80):
+        b = bytearray(x.to_bytes(48, "big"))
+        b[0] |= flags
+        return bytes(b)
+
+    xv = 1
+    while O.g1_decompress(enc1(O.P - xv))[0] != O.SUCCESS:
+        xv += 1
+    gl = [
+        ("x = p-1", enc1(O.P - 1)),
+        ("x = p-1, sign bit", enc1(O.P - 1, 0xA0)),
+        ("largest x on the curve", enc1(O.P - xv)),
+        ("largest x on the curve, sign bit", enc1(O.P - xv, 0xA0)),
+        ("x = p", enc1(O.P)),
+        ("x = p, sign bit", enc1(O.P, 0xA0)),
+        ("x = p+1", enc1(O.P + 1)),
+        ("x = 2^381-1", bytes([0x9F]) + b"\xff" * 47),
+        ("0xa0 then zeros", bytes([0xA0]) + bytes(47)),
+        ("0xa0 on the generator", enc1(O.G1_GEN[0], 0xA0)),
+        ("generator", enc1(O.G1_GEN[0])),
+        ("0xe0 then zeros", bytes([0xE0]) + bytes(47)),
+        ("infinity, non-zero byte", bytes([0xC0]) + bytes(30) + b"\x80" + bytes(16)),
+        ("compression bit clear", enc1(O.G1_GEN[0], 0x00)),
+        ("all 0xff", b"\xff" * 48),
+    ]
+    gcases = []
+    for note, b in gl:
+        st, pt = O.g1_decompress(b)
+        rec = {"note": note, "in": b.hex(), "status": st, "validate_status": O.public_key_from_bytes(b)[0]}
+        if st == O.SUCCESS and pt is not None:
+            rec.update({"x": "%096x" % pt[0], "y": "%096x" % pt[1]})
+        gcases.append(rec)
+    edges = {"provenance": "oracle (blst POINTonE2_Uncompress_Z / POINTonE1_Uncompress_Z) on seeded constructions: "
+                           "x0^2 = (x1^3 - 4)/(3 x1) makes y^2 real, x1^2 = (x0^3 + 4)/(3 x0) makes it imaginary",
+             "g2_roots": rcases, "g2_flags": fcases, "g1_flags": gcases}
+    for name, obj in (("small_order", small), ("decode_edges", edges)):
+        with open(os.path.join(HERE, name + ".json"), "w") as fh:
+            json.dump(obj, fh, indent=1)
+    print("edge fixtures written: small_order decode_edges", count)
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["edges"]:
+        edges_main()
+    else:
+        main()
