@@ -151,6 +151,19 @@ EXPORTS_MSGCACHE_CHECKS = [
     "gbls_msgcache_serve_checks",
     "gbls_msgcache_checks_stats",
 ]
+# include/grandine_bls_gpu_telemetry.h (engine telemetry: call phases, merge sizes, memory held)
+EXPORTS_TELEMETRY = [
+    "gbls_telemetry_enable",
+    "gbls_telemetry_read",
+    "gbls_telemetry_reset",
+    "gbls_telemetry_trace",
+    "gbls_telemetry_memory",
+    "gbls_telemetry_phase_name",
+    "gbls_telemetry_kind_name",
+    "gbls_telemetry_class_name",
+]
+TELEMETRY_CLASSES, TELEMETRY_KINDS, TELEMETRY_PHASES, TELEMETRY_CALLER_PHASES = 2, 9, 13, 5
+TELEMETRY_BUCKETS, TELEMETRY_BINS, TELEMETRY_TRACE_CAPACITY, TELEMETRY_MAX_ENGINES = 32, 24, 1024, 16
 MSGCACHE_CHECKS_STATS = ("prefetched", "check_lookups", "check_hits", "check_published")
 PREFETCH_ENTERED, PREFETCH_PRESENT, PREFETCH_SKIPPED = 0, 1, 2
 MSGCACHE_STATS = ("lookups", "hits", "misses", "published", "evictions", "bypassed", "entries", "reserved")
@@ -158,6 +171,44 @@ MSGCACHE_STATS = ("lookups", "hits", "misses", "published", "evictions", "bypass
 
 class EngineUnavailable(RuntimeError):
     pass
+
+
+_u32, _u64 = ctypes.c_uint32, ctypes.c_uint64
+
+
+class TelemetryHist(ctypes.Structure):
+    _fields_ = [("count", _u64), ("sum_ns", _u64), ("max_ns", _u64), ("bucket", _u64 * TELEMETRY_BUCKETS)]
+
+
+class TelemetryCell(ctypes.Structure):
+    _fields_ = [(n, _u64) for n in ("calls", "sets", "rejected", "engine_errors", "submissions", "shards", "callers",
+                                    "submitted_sets", "fresh_contexts", "staging_waits", "growths", "reserved")] + [
+        ("callers_bin", _u64 * TELEMETRY_BINS), ("sets_bin", _u64 * TELEMETRY_BINS),
+        ("phase", TelemetryHist * TELEMETRY_PHASES)]
+
+
+class TelemetrySnapshot(ctypes.Structure):
+    _fields_ = [("size", _u32), ("level", _u32), ("trace_written", _u64), ("trace_dropped", _u64),
+                ("cell", (TelemetryCell * TELEMETRY_KINDS) * TELEMETRY_CLASSES)]
+
+
+class TelemetryRecord(ctypes.Structure):
+    _fields_ = [("id", _u64), ("submission", _u64), ("cls", _u32), ("kind", _u32), ("callers", _u32), ("segments", _u32),
+                ("sets", _u64), ("shard_sets", _u64), ("engine", _u32), ("fresh", _u32), ("context", _u64),
+                ("first_arrival_ns", _u64), ("lead_ns", _u64), ("lease_ns", _u64), ("first_event_ns", _u64),
+                ("enqueued_ns", _u64), ("synced_ns", _u64), ("staging_wait_ns", _u64), ("staging_waits", _u32),
+                ("growths", _u32), ("device_ns", _u64), ("lag_ns", _u64)]
+
+
+class TelemetryEngineMemory(ctypes.Structure):
+    _fields_ = [("hip_device", _u32), ("reserved", _u32), ("contexts_leased", _u64 * TELEMETRY_CLASSES),
+                ("contexts_idle", _u64 * TELEMETRY_CLASSES), ("workspace_bytes", _u64 * TELEMETRY_CLASSES)] + [
+        (n, _u64) for n in ("registry_bytes", "committee_bytes", "member_bytes", "linecache_bytes", "pinned_live_bytes",
+                            "pinned_retired_bytes", "pinned_retired_buffers", "device_free_bytes", "device_total_bytes")]
+
+
+class TelemetryMemoryInfo(ctypes.Structure):
+    _fields_ = [("size", _u32), ("engines", _u32), ("engine", TelemetryEngineMemory * TELEMETRY_MAX_ENGINES)]
 
 
 _lock = threading.Lock()
@@ -271,13 +322,21 @@ def load_library():
                 "gbls_msgcache_prefetch": (_c.c_int, [_vp, _sz, _vp]),
                 "gbls_msgcache_serve_checks": (_c.c_int, [_c.c_int]),
                 "gbls_msgcache_checks_stats": (_c.c_int, [_vp]),
+                "gbls_telemetry_enable": (_c.c_int, [_c.c_int]),
+                "gbls_telemetry_read": (_c.c_int, [_c.POINTER(TelemetrySnapshot), _sz]),
+                "gbls_telemetry_reset": (None, []),
+                "gbls_telemetry_trace": (_sz, [_c.POINTER(TelemetryRecord), _sz, _c.POINTER(_c.c_uint64)]),
+                "gbls_telemetry_memory": (_c.c_int, [_c.POINTER(TelemetryMemoryInfo), _sz]),
+                "gbls_telemetry_phase_name": (_c.c_char_p, [_c.c_int]),
+                "gbls_telemetry_kind_name": (_c.c_char_p, [_c.c_int]),
+                "gbls_telemetry_class_name": (_c.c_char_p, [_c.c_int]),
             }
             for name, (res, args) in sig.items():
                 # an experiment build (GBLS_LIB) may predate the message line cache (or its
-                # per-check extension), the bits, the spans, the each, the local or the fold calls: A/B tools
+                # per-check extension), the bits, the spans, the each, the local, the fold or the telemetry calls: A/B tools
                 # load it and leave those entries alone; the package's own library must have them
                 if (_override and name in EXPORTS_MSGCACHE + EXPORTS_MSGCACHE_CHECKS + EXPORTS_BITS + EXPORTS_SPANS
-                        + EXPORTS_EACH + EXPORTS_LOCAL + EXPORTS_FOLD and not hasattr(lib, name)):
+                        + EXPORTS_EACH + EXPORTS_LOCAL + EXPORTS_FOLD + EXPORTS_TELEMETRY and not hasattr(lib, name)):
                     continue
                 fn = getattr(lib, name)
                 fn.restype = res

@@ -42,6 +42,7 @@
 #include "../../include/grandine_bls_gpu_spans.h"
 #include "../../include/grandine_bls_gpu_local.h"
 #include "../../include/grandine_bls_gpu_fold.h"
+#include "../../include/grandine_bls_gpu_telemetry.h"
 #include "gbls_common.h"
 #include "gbls_bits.h"
 #include "gbls_committees.h"
@@ -54,6 +55,7 @@
 #include "gbls_local.h"
 #include "gbls_fold.h"
 #include "gbls_tables.h"
+#include "gbls_telemetry.h"
 
 using namespace gbls;
 
@@ -227,6 +229,101 @@ struct StageTimer {  // RAII: events around one stage's launches when profiling
   }
 };
 
+
+// ---------------------------------------------------------------- engine telemetry
+// (include/grandine_bls_gpu_telemetry.h; the recording structures are gbls_telemetry.h.)  At level 0
+// every hook below is a thread-local read or one relaxed load of the level: no clock, no event.
+tel::Store g_tel;
+inline int tel_level() { return g_tel.level.load(std::memory_order_relaxed); }
+uint64_t tel_now() {
+  return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(
+             std::chrono::steady_clock::now().time_since_epoch())
+      .count();
+}
+// one submission: a merged verification of the coalescer, or the implicit one of a direct or device
+// call (one caller)
+struct TelSub {
+  uint64_t id = 0;
+  int cls = 0, kind = tel::K_DIRECT;
+  uint32_t callers = 1;
+  uint64_t sets = 0, first_arrival = 0, lead = 0;
+  uint64_t reglock_ns = 0;  // waited for the registry's shared lock: charged to the next shard
+};
+// one API call of this thread (the outermost entry: an entry reached through another entry only
+// refines the kind, the class and the sets)
+struct TelCall {
+  int cls = 0, kind = tel::K_DIRECT;
+  uint64_t sets = 0, t0 = 0;
+  sched::CallPhases ph;
+  bool coalesced = false, worked = false, sub_open = false;
+  TelSub sub;
+  uint64_t run_last = 0;
+};
+thread_local TelCall *t_call = nullptr;
+thread_local TelSub *t_sub = nullptr;
+// one shard: a context lease of a submission
+struct TelShard {
+  TelSub *sub = nullptr;
+  uint64_t t_begin = 0, t_lease = 0, t_first_event = 0, t_enqueued = 0, t_wait = 0, t_synced = 0;
+  uint64_t growth_ns = 0, reglock_ns = 0, excl_ns = 0;
+  tel::StagingWaits staging;
+  uint32_t growths = 0, segments = 0;
+  uint64_t sets = 0;
+  hipEvent_t ev_a = nullptr, ev_b = nullptr;  // level 2: around the shard on its main stream
+  bool ev_a_set = false, ev_b_set = false;
+  bool own_wait = true;  // the host waits on this shard's stream (false: behind another shard's, no sync sample of its own)
+};
+// the submission a lease made now belongs to (opens the call's implicit one); null: not recorded
+TelSub *tel_current_sub() {
+  if (t_sub) return t_sub;
+  TelCall *tc = t_call;
+  if (!tc) return nullptr;
+  if (!tc->sub_open) {
+    tc->sub_open = true;
+    tc->sub.id = g_tel.next_submission.fetch_add(1, std::memory_order_relaxed);
+    tc->sub.first_arrival = tc->t0;
+    tc->sub.lead = tel_now();
+  }
+  tc->worked = true;
+  tc->sub.cls = tc->cls;
+  tc->sub.kind = tc->kind;
+  tc->sub.sets = tc->sets;
+  return &tc->sub;
+}
+struct TelScope {  // RAII at an API entry
+  TelCall call;
+  bool owner = false;
+  TelScope(int kind, int cls, uint64_t sets) {
+    if (TelCall *tc = t_call) {
+      tc->kind = kind, tc->cls = cls ? 1 : 0, tc->sets = sets;
+      return;
+    }
+    if (tel_level() == 0) return;
+    owner = true;
+    call.kind = kind, call.cls = cls ? 1 : 0, call.sets = sets;
+    call.t0 = tel_now();
+    t_call = &call;
+  }
+  ~TelScope() {
+    if (!owner) return;
+    t_call = nullptr;
+    const int err = t_last_error;
+    if (err == GBLS_ERR_ARG && !call.worked) {
+      g_tel.record_rejected(call.cls, call.kind);
+      return;
+    }
+    const uint64_t t1 = tel_now();
+    tel::CallTimes ct{0, 0, 0, 0, t1 - call.t0};
+    if (call.coalesced)
+      ct = tel::call_times(call.ph, call.t0, t1);
+    else if (call.sub_open)
+      ct.run = call.run_last - call.sub.lead;
+    g_tel.record_call(call.cls, call.kind, call.sets, ct, err != GBLS_ERR_NONE);
+    if (call.sub_open) g_tel.record_submission(call.cls, call.kind, 1, call.sets);
+  }
+};
+#define TEL_CALL(kind, cls, sets) TelScope tel_scope_((kind), (cls), (uint64_t)(sets))
+
 // ---------------------------------------------------------------- per-call context
 struct Ctx {
   int hipdev = -1;
@@ -256,6 +353,11 @@ struct Ctx {
   hipEvent_t ev_reg = nullptr;
   bool reg_read = false;
   int cls = 0;                        // 0: normal, 1: block import (every stream high priority)
+  TelShard *tel = nullptr;            // telemetry of the lease that holds this context (null: none)
+  std::atomic<bool> leased{false};    // a Lease holds it (the memory gauges count leased and idle)
+  // memory gauges: the sum of every workspace's Buf::cap, the staging ring's slots, and the retired
+  // staging buffers (written by the leaseholder, read by gbls_telemetry_memory under the pool mutex)
+  std::atomic<uint64_t> ws_bytes{0}, pinned_live{0}, pinned_retired{0}, pinned_retired_n{0};
   bool active = false;                // a call holds the lease and has begun
   hipStream_t cur = nullptr;          // its main stream (nullptr = the legacy default stream)
   bool used = false;                  // last_stream is meaningful
@@ -365,11 +467,16 @@ struct Ctx {
       if (trace_stalls())
         fprintf(stderr, "gbls: call %llu ctx %p%s waits for staging slot %d\n", call_id, (void *)this,
                 fresh ? " (fresh)" : "", stage_at);
-      HIPCHK(hipEventSynchronize(r.ev));
+      HIPCHK(tel::timed_wait(tel_now, tel ? &tel->staging : nullptr, [&] { return hipEventSynchronize(r.ev); }));
       r.pending = false;
     }
     stage_used = 0;
     if (done_pending) HIPCHK(hipStreamWaitEvent(st, ev_done, 0));
+    if (tel && tel->ev_a) {  // level 2: the shard's first timing event, at the head of its main stream
+      HIPCHK(hipEventRecord(tel->ev_a, st));
+      tel->ev_a_set = true;
+      tel->t_first_event = tel_now();
+    }
     return true;
   }
   // true when the previous call on this context has finished on the GPU
@@ -401,11 +508,21 @@ struct Ctx {
     if (trace_stalls())
       fprintf(stderr, "gbls: call %llu ctx %p%s grows a buffer %zu -> %zu bytes (%s)\n", call_id, (void *)this,
               fresh ? " (fresh)" : "", b.cap, bytes, g_stream_alloc ? "stream-ordered" : "host wait");
-    if (g_stream_alloc) return grow_async(b, bytes) || fail(GBLS_ERR_HIP);
-    if (!drain()) return false;
+    if (tel) tel->growths++;
+    const uint64_t old = b.cap;
+    if (g_stream_alloc) {
+      const bool ok = grow_async(b, bytes);
+      ws_bytes.fetch_add((uint64_t)b.cap - old, std::memory_order_relaxed);
+      return ok || fail(GBLS_ERR_HIP);
+    }
+    const uint64_t w0 = tel ? tel_now() : 0;  // the growth that waits on the host
+    bool ok = drain();
     // an in-flight stage of THIS call may still read the old buffer
-    if (active) HIPCHK(hipStreamSynchronize(cur));
-    return b.ensure(bytes) || fail(GBLS_ERR_HIP);
+    if (ok && active && hipStreamSynchronize(cur) != hipSuccess) ok = fail(GBLS_ERR_HIP);
+    if (ok) ok = b.ensure(bytes) || fail(GBLS_ERR_HIP);
+    ws_bytes.fetch_add((uint64_t)b.cap - old, std::memory_order_relaxed);
+    if (tel) tel->growth_ns += tel_now() - w0;
+    return ok;
   }
   // Growth without a host wait: the old buffer is freed on `own` behind the previous call on this
   // context (ev_done) and behind everything this call has enqueued so far on its other streams;
@@ -449,7 +566,8 @@ struct Ctx {
         if (trace_stalls())
           fprintf(stderr, "gbls: call %llu ctx %p%s waits for staging slot %d to grow it\n", call_id,
                   (void *)this, fresh ? " (fresh)" : "", stage_at);
-        if (hipEventSynchronize(r.ev) != hipSuccess) return nullptr;
+        if (tel::timed_wait(tel_now, tel ? &tel->staging : nullptr, [&] { return hipEventSynchronize(r.ev); }) != hipSuccess)
+          return nullptr;
         r.pending = false;
       }
       if (need > r.cap) {
@@ -466,11 +584,17 @@ struct Ctx {
           if (trace_stalls())
             fprintf(stderr, "gbls: call %llu ctx %p%s grows staging slot %d %zu -> %zu bytes\n", call_id,
                     (void *)this, fresh ? " (fresh)" : "", q, o.cap, want);
-          if (o.p) retired_host.push_back(o.p);
+          if (o.p) {
+            retired_host.push_back(o.p);
+            pinned_retired.fetch_add(o.cap, std::memory_order_relaxed);
+            pinned_retired_n.fetch_add(1, std::memory_order_relaxed);
+            pinned_live.fetch_sub(o.cap, std::memory_order_relaxed);
+          }
           o.p = nullptr;
           o.cap = 0;
           if (hipHostMalloc(&o.p, want, hipHostMallocDefault) != hipSuccess) return nullptr;
           o.cap = want;
+          pinned_live.fetch_add(want, std::memory_order_relaxed);
         }
       }
       stage_used = 0;
@@ -514,6 +638,7 @@ struct McTable {
   uint32_t *dev = nullptr;
   int hipdev = -1;
   uint64_t gen = 0;
+  size_t bytes = 0;  // of dev
   ~McTable() {
     if (!dev) return;
     int cur = -1;
@@ -566,10 +691,51 @@ struct Device {
   struct MemBlock {
     void *p = nullptr;
     bool pooled = false;
+    size_t bytes = 0;
   };
   std::vector<MemBlock> mem_blocks;
   std::shared_ptr<McTable> mc_tab;  // message line cache table (guarded by mcache.mu)
+  // telemetry level 2: timing events of this device, created when the level is switched on (or by
+  // gbls_init under it) and reused, so that no hipEventCreate runs inside a timed call (see Prof)
+  std::mutex tel_mu;
+  std::vector<hipEvent_t> tel_ev;
+  int index = 0;  // position in Engine::devs
+  bool tel_take(hipEvent_t &a, hipEvent_t &b) {
+    {
+      std::lock_guard<std::mutex> lk(tel_mu);
+      if (tel_ev.size() >= 2) {
+        a = tel_ev.back(), tel_ev.pop_back();
+        b = tel_ev.back(), tel_ev.pop_back();
+        return true;
+      }
+    }
+    if (hipEventCreate(&a) != hipSuccess) return false;
+    if (hipEventCreate(&b) != hipSuccess) {
+      (void)hipEventDestroy(a);
+      return false;
+    }
+    return true;
+  }
+  void tel_give(hipEvent_t a, hipEvent_t b) {
+    std::lock_guard<std::mutex> lk(tel_mu);
+    tel_ev.push_back(a);
+    tel_ev.push_back(b);
+  }
+  bool tel_fill(size_t want) {  // up to `want` events at hand
+    std::lock_guard<std::mutex> lk(tel_mu);
+    int cur = -1;
+    (void)hipGetDevice(&cur);
+    bool ok = hipSetDevice(hipdev) == hipSuccess;
+    while (ok && tel_ev.size() < want) {
+      hipEvent_t e = nullptr;
+      ok = hipEventCreate(&e) == hipSuccess;
+      if (ok) tel_ev.push_back(e);
+    }
+    if (cur >= 0) (void)hipSetDevice(cur);
+    return ok;
+  }
 };
+constexpr size_t kTelEvents = 128;  // per engine device: 64 shards in flight
 
 struct Engine {
   std::mutex mu;
@@ -614,9 +780,21 @@ struct Engine {
 class Lease {
  public:
   Lease(Device &d, bool affine, hipStream_t stream, int cls = 0) : d_(d) {
-    c_ = d.pool.acquire(affine, stream, cls, &fresh_);
+    TelSub *sub = tel_current_sub();
+    c_ = tel::timed_acquire(d.pool, affine, stream, cls, &fresh_, sub ? tel_now : nullptr, &tel_.t_begin, &tel_.t_lease);
+    c_->leased.store(true, std::memory_order_relaxed);
     c_->call_id = g_lease_calls.fetch_add(1);
     c_->fresh = fresh_ || !c_->used;  // created now, or created by gbls_init and never used
+    c_->tel = nullptr;
+    if (sub) {
+      tel_.sub = sub;
+      tel_.reglock_ns = sub->reglock_ns;
+      sub->reglock_ns = 0;
+      // level 2: device time of the shard (never for the device kind, which must not synchronise)
+      if (tel_level() >= 2 && sub->kind != tel::K_DEVICE && !d.tel_take(tel_.ev_a, tel_.ev_b))
+        tel_.ev_a = tel_.ev_b = nullptr;
+      c_->tel = &tel_;
+    }
     if (fresh_ && trace_stalls())
       fprintf(stderr, "gbls: call %llu creates ctx %p (class %d, %zu contexts)\n", c_->call_id, (void *)c_,
               c_->cls, d.pool.size());
@@ -624,7 +802,23 @@ class Lease {
                  : (hipSetDevice(d.hipdev) == hipSuccess || fail(GBLS_ERR_HIP));
   }
   explicit Lease(Device &d, int cls = 0) : Lease(d, false, nullptr, cls) {}
+  // telemetry: the shard's last launch is enqueued (level 2: the timing event behind its work)
+  void tel_enqueued() {
+    if (!c_->tel || tel_.t_enqueued) return;
+    if (tel_.ev_a_set && hipEventRecord(tel_.ev_b, c_->cur) == hipSuccess) tel_.ev_b_set = true;
+    tel_.t_enqueued = tel_now();
+  }
+  // ... the host starts to wait for it (the sync phase is this wait alone: between a shard's last
+  // launch and its wait the host may enqueue the submission's other shards), and the wait is over
+  void tel_waiting() {
+    if (c_->tel && !tel_.t_wait) tel_.t_wait = tel_now();
+  }
+  void tel_synced() {
+    if (c_->tel && !tel_.t_synced) tel_.t_synced = tel_now();
+  }
+  TelShard *tel() { return c_->tel; }
   ~Lease() {
+    if (c_->tel) tel_finish();
     if (c_->active) {
       if (hipEventRecord(c_->ev_done, c_->cur) == hipSuccess) c_->done_pending = true;
       c_->last_stream = c_->cur;
@@ -632,6 +826,7 @@ class Lease {
       c_->active = false;
       c_->cur = nullptr;
     }
+    c_->leased.store(false, std::memory_order_relaxed);
     d_.pool.release(c_);
   }
   bool ok() const { return ok_; }
@@ -642,7 +837,53 @@ class Lease {
   Device &d_;
   Ctx *c_ = nullptr;
   bool fresh_ = false, ok_ = false;
+  TelShard tel_;
+  void tel_finish() {
+    c_->tel = nullptr;
+    TelSub &sub = *tel_.sub;
+    const bool device_kind = sub.kind == tel::K_DEVICE;
+    tel_enqueued();  // (a path that marked nothing: everything up to here was enqueueing)
+    if (device_kind) tel_.t_synced = tel_.t_enqueued;  // no host wait: no sync sample
+    tel_synced();
+    if (!tel_.t_wait) tel_.t_wait = tel_.t_enqueued;
+    gbls_telemetry_record r{};
+    r.submission = sub.id;
+    r.cls = (uint32_t)sub.cls, r.kind = (uint32_t)sub.kind;
+    r.callers = sub.callers, r.segments = tel_.segments;
+    r.sets = sub.sets, r.shard_sets = tel_.sets ? tel_.sets : sub.sets;
+    r.engine = (uint32_t)d_.index, r.fresh = c_->fresh ? 1 : 0;
+    r.context = (uint64_t)reinterpret_cast<uintptr_t>(c_);
+    r.first_arrival_ns = sub.first_arrival, r.lead_ns = sub.lead, r.lease_ns = tel_.t_lease;
+    r.first_event_ns = tel_.t_first_event, r.enqueued_ns = tel_.t_enqueued, r.synced_ns = tel_.t_synced;
+    r.staging_wait_ns = tel_.staging.ns, r.staging_waits = tel_.staging.count, r.growths = tel_.growths;
+    if (tel_.ev_a_set && tel_.ev_b_set) {
+      float ms = 0;
+      if (hipEventElapsedTime(&ms, tel_.ev_a, tel_.ev_b) == hipSuccess && ms > 0) {
+        // both events lie inside [first event recorded, synced]; the clamp only absorbs the rounding
+        // of the elapsed time (a float in milliseconds)
+        const uint64_t seen = r.synced_ns - r.first_event_ns;
+        r.device_ns = std::min<uint64_t>((uint64_t)((double)ms * 1e6), seen);
+        r.lag_ns = seen - r.device_ns;
+      } else {
+        (void)hipGetLastError();
+      }
+    }
+    if (tel_.ev_a) d_.tel_give(tel_.ev_a, tel_.ev_b);
+    const uint64_t busy = r.enqueued_ns - r.lease_ns;
+    g_tel.record_shard(r, tel_.reglock_ns, tel_.t_lease - tel_.t_begin, tel_.growth_ns,
+                       busy > tel_.excl_ns ? busy - tel_.excl_ns : 0, tel_.own_wait ? r.synced_ns - tel_.t_wait : 0,
+                       !device_kind);
+    if (TelCall *tc = t_call) tc->run_last = tel_now();
+  }
 };
+// a direct call's host wait on its main stream, with the shard's enqueued and synced marks
+hipError_t tel_stream_sync(Lease &L, hipStream_t st) {
+  L.tel_enqueued();
+  L.tel_waiting();
+  const hipError_t e = hipStreamSynchronize(st);
+  L.tel_synced();
+  return e;
+}
 
 bool registry_streams(Device &d);
 
@@ -743,6 +984,7 @@ bool engine_init(uint32_t device_mask, uint32_t flags) {
       g.devs.back()->hipdev = id;
       g.devs.back()->nsimd = 4u * (uint32_t)prop.multiProcessorCount;
       g.devs.back()->ncu = prop.multiProcessorCount;
+      g.devs.back()->index = (int)g.devs.size() - 1;
     }
   }
   (void)hipGetLastError();
@@ -799,6 +1041,8 @@ bool engine_init(uint32_t device_mask, uint32_t flags) {
         (void)hipDeviceEnablePeerAccess(b, 0);  // "already enabled" is fine
     }
   (void)hipGetLastError();
+  if (tel_level() >= 2)
+    for (auto &dp : g.devs) (void)dp->tel_fill(kTelEvents);
   g.ready.store(true);
   return true;
 }
@@ -1616,6 +1860,7 @@ bool mc_table(Device &d, std::shared_ptr<McTable> *old) {
     (void)hipGetLastError();
     return fail(GBLS_ERR_HIP);
   }
+  t->bytes = (mcache.slots + spare) * msgcache::kSlotWords * 4;
   t->ix.reset((uint32_t)mcache.slots, spare, mcache.st);
   d.mc_tab = std::move(t);
   return true;
@@ -1682,6 +1927,7 @@ bool enqueue_host_batch(Ctx &c, Device &d, const uint8_t *msgs, const g2a *sigs,
   hipStream_t st = c.own;
   size_t n = e - b;
   if (key_status && !src.cbits) return fail(GBLS_ERR_ARG);  // the statuses of a span source only
+  if (c.tel) c.tel->sets = n, c.tel->segments = (uint32_t)nseg;
   if (!c.begin(st)) return false;
   const bool single = rands == nullptr;
   // GBLS_INIT_DEDUP: this shard's sets grouped by message (per segment).  Without duplicates, or
@@ -1815,7 +2061,10 @@ bool verify_host(const uint8_t *msgs, const g2a *sigs, const uint8_t *sigs_c, in
                  const PkSource &src, const uint64_t *rands, size_t n, const uint32_t *seg_off,
                  size_t nseg, int32_t *verdicts, int cls = 0, int32_t *key_status = nullptr,
                  int32_t *pkb_status = nullptr) {
+  TelSub *tsub = tel_current_sub();
+  const uint64_t tl0 = tsub ? tel_now() : 0;
   std::shared_lock<std::shared_mutex> rl(g.reg_mu);
+  if (tsub) tsub->reglock_ns += tel_now() - tl0;
   const size_t ndev = g.devs.size();
   // ---- one large batch: per-device Miller partials, gathered device-to-device onto device 0
   // (hipMemcpyPeerAsync over xGMI, ordered by events, no host round trip), one final
@@ -1835,6 +2084,7 @@ bool verify_host(const uint8_t *msgs, const g2a *sigs, const uint8_t *sigs_c, in
     std::vector<std::unique_ptr<Lease>> leases;
     std::vector<hipEvent_t> evs;
     bool ok = true;
+    const uint64_t tp0 = L0.tel() ? tel_now() : 0;  // the shards' enqueueing is theirs, not the final's
     for (size_t j = 0; j < k && ok; j++) {
       size_t b = n * j / k, e = n * (j + 1) / k;
       Device &d = *g.devs[j];
@@ -1852,7 +2102,10 @@ bool verify_host(const uint8_t *msgs, const g2a *sigs, const uint8_t *sigs_c, in
       }
       evs.push_back(ev);
       if (hipEventRecord(ev, L->own) != hipSuccess) ok = fail(GBLS_ERR_HIP);
+      L.tel_enqueued();
+      if (L.tel()) L.tel()->own_wait = false;
     }
+    if (L0.tel()) L0.tel()->excl_ns += tel_now() - tp0;
     if (ok && hipSetDevice(d0.hipdev) != hipSuccess) ok = fail(GBLS_ERR_HIP);
     for (size_t j = 0; ok && j < evs.size(); j++)
       if (hipStreamWaitEvent(st0, evs[j], 0) != hipSuccess) ok = fail(GBLS_ERR_HIP);
@@ -1860,12 +2113,16 @@ bool verify_host(const uint8_t *msgs, const g2a *sigs, const uint8_t *sigs_c, in
                               L0->out1.as<int32_t>(), st0);
     if (ok && hipMemcpyAsync(verdicts, L0->out1.p, 4, hipMemcpyDeviceToHost, st0) != hipSuccess)
       ok = fail(GBLS_ERR_HIP);
+    L0.tel_enqueued();
     rl.unlock();  // enqueued: the host wait does not hold up registry updates
     // the final's stream waited on every shard, so its completion covers theirs (including the
     // shards' signature-status copies to the host); on a failure every shard is drained
+    L0.tel_waiting();
     if (ok && hipStreamSynchronize(st0) != hipSuccess) ok = fail(GBLS_ERR_HIP);
     if (!ok)
       for (auto &L : leases) (void)hipStreamSynchronize((*L)->own);
+    L0.tel_synced();  // the shards' host wait was the final's
+    for (auto &L : leases) L->tel_synced();
     // message line cache: every shard's misses are published on the batch's verdict
     for (auto &L : leases) mc_finish(**L, nullptr, ok && verdicts[0] == GBLS_SUCCESS);
     for (hipEvent_t ev : evs) (void)hipEventDestroy(ev);
@@ -1898,10 +2155,14 @@ bool verify_host(const uint8_t *msgs, const g2a *sigs, const uint8_t *sigs_c, in
     ok = L.ok() && enqueue_host_batch(*L, d, msgs, sigs, sigs_c, sig_status, src, rands, b, e,
                                       segs[j].data(), s1 - s0, verdicts + s0, nullptr, nullptr, 0,
                                       key_status, pkb_status);
+    L.tel_enqueued();
   }
   rl.unlock();  // enqueued: the host waits do not hold up registry updates
-  for (auto &L : leases)
+  for (auto &L : leases) {
+    L->tel_waiting();
     if (hipStreamSynchronize((*L)->own) != hipSuccess) ok = fail(GBLS_ERR_HIP);
+    L->tel_synced();
+  }
   // message line cache: each shard publishes the misses of its segments that passed
   for (size_t j = 0, l = 0; j < k && l < leases.size(); j++) {
     if (cut[j + 1] == cut[j]) continue;
@@ -1930,10 +2191,28 @@ bool coalesced_verify(CoReq &r) {
   cfg.merge_target = g.merge_target;
   cfg.merge_window_us = g.merge_window_us;
   if (g.block_hold) cfg.hold = &g.block_active;
+  if (TelCall *tc = t_call) {  // telemetry: this caller's phases, stamped by the scheduler
+    tc->kind = tel::kind_of(r), tc->cls = r.prio ? 1 : 0, tc->sets = r.n;
+    tc->coalesced = tc->worked = true;
+    r.ph = &tc->ph;
+    cfg.clock = tel_now;
+  }
   bool ok = co.submit(r, cfg, [](CoReq &m) {
+    TelSub sub, *outer = t_sub;
+    if (m.bi) {  // the submission this leader runs: every lease below is one of its shards
+      sub.id = g_tel.next_submission.fetch_add(1, std::memory_order_relaxed);
+      sub.cls = m.prio ? 1 : 0, sub.kind = tel::kind_of(m);
+      sub.callers = m.bi->callers, sub.sets = m.n;
+      sub.first_arrival = m.bi->first_arrival_ns, sub.lead = m.bi->lead_ns;
+      t_sub = &sub;
+    }
     m.ok = verify_host(m.msgs, m.sigs, m.sigs_c, m.sig_status, m.src, m.rands, m.n, m.seg_off,
                        m.nseg, m.verdicts, m.prio, m.key_status, m.pkb_status);
     m.err = t_last_error;  // the leader's thread-local code, handed to every merged caller
+    if (m.bi) {
+      t_sub = outer;
+      g_tel.record_submission(sub.cls, sub.kind, sub.callers, sub.sets);
+    }
   });
   t_last_error = r.err;
   return ok;
@@ -2102,6 +2381,7 @@ bool block_upload(Ctx &c, Device &d, uint32_t id, const void *host, size_t bytes
     mb.p = nullptr;
     HIPCHK(hipMalloc(&mb.p, bytes + 16));
   }
+  mb.bytes = bytes + 16;
   return c.upload_to(mb.p, host, bytes, d.reg_st);
 }
 // Free d's memory of a dead block behind the work that may still read it: what d.reg_st holds (the
@@ -2178,6 +2458,7 @@ int gbls_device_count(void) { return g.ready.load() ? (int)g.devs.size() : 0; }
 
 int gbls_g1_decompress(const uint8_t (*in)[48], size_t n, int validate, gbls_p1_affine *out,
                        int32_t *status) {
+  TEL_CALL(tel::K_DIRECT, 0, n);
   fill(status, n, GBLS_BAD_ENCODING);
   API_BEGIN
   if (n == 0) return GBLS_SUCCESS;
@@ -2191,7 +2472,7 @@ int gbls_g1_decompress(const uint8_t (*in)[48], size_t n, int validate, gbls_p1_
                        c.out1.as<int32_t>());
   if (hipMemcpyAsync(out, c.out0.p, n * sizeof(g1a), hipMemcpyDeviceToHost, st) != hipSuccess ||
       hipMemcpyAsync(status, c.out1.p, n * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess) {
+      tel_stream_sync(L, st) != hipSuccess) {
     fill(status, n, GBLS_BAD_ENCODING);
     return fail(GBLS_ERR_HIP), FAILED;
   }
@@ -2199,6 +2480,7 @@ int gbls_g1_decompress(const uint8_t (*in)[48], size_t n, int validate, gbls_p1_
 }
 
 int gbls_g2_decompress(const uint8_t (*in)[96], size_t n, gbls_p2_affine *out, int32_t *status) {
+  TEL_CALL(tel::K_DIRECT, 0, n);
   fill(status, n, GBLS_BAD_ENCODING);
   API_BEGIN
   if (n == 0) return GBLS_SUCCESS;
@@ -2212,7 +2494,7 @@ int gbls_g2_decompress(const uint8_t (*in)[96], size_t n, gbls_p2_affine *out, i
                        c.out1.as<int32_t>());
   if (hipMemcpyAsync(out, c.out0.p, n * sizeof(g2a), hipMemcpyDeviceToHost, st) != hipSuccess ||
       hipMemcpyAsync(status, c.out1.p, n * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess) {
+      tel_stream_sync(L, st) != hipSuccess) {
     fill(status, n, GBLS_BAD_ENCODING);
     return fail(GBLS_ERR_HIP), FAILED;
   }
@@ -2220,6 +2502,7 @@ int gbls_g2_decompress(const uint8_t (*in)[96], size_t n, gbls_p2_affine *out, i
 }
 
 int gbls_g2_validate(const gbls_p2_affine *in, size_t n, int32_t *status) {
+  TEL_CALL(tel::K_DIRECT, 0, n);
   fill(status, n, GBLS_POINT_NOT_IN_GROUP);
   API_BEGIN
   if (n == 0) return GBLS_SUCCESS;
@@ -2231,7 +2514,7 @@ int gbls_g2_validate(const gbls_p2_affine *in, size_t n, int32_t *status) {
     return FAILED;
   launch_g2_check(st, c.in0.as<g2a>(), (uint32_t)n, c.out1.as<int32_t>(), 0);
   if (hipMemcpyAsync(status, c.out1.p, n * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess) {
+      tel_stream_sync(L, st) != hipSuccess) {
     fill(status, n, GBLS_POINT_NOT_IN_GROUP);
     return fail(GBLS_ERR_HIP), FAILED;
   }
@@ -2240,6 +2523,7 @@ int gbls_g2_validate(const gbls_p2_affine *in, size_t n, int32_t *status) {
 
 static int compress_impl(const void *in, size_t n, size_t in_sz, size_t out_sz, uint8_t *out,
                          int which) {
+  TEL_CALL(tel::K_DIRECT, 0, n);
   API_BEGIN
   if (n == 0) return GBLS_SUCCESS;
   Lease L(pick_device());
@@ -2253,7 +2537,7 @@ static int compress_impl(const void *in, size_t n, size_t in_sz, size_t out_sz, 
   else
     launch_g2_compress(st, c.in0.as<g2a>(), (uint32_t)n, c.out0.as<uint8_t>());
   if (hipMemcpyAsync(out, c.out0.p, n * out_sz, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess)
+      tel_stream_sync(L, st) != hipSuccess)
     return fail(GBLS_ERR_HIP), FAILED;
   return GBLS_SUCCESS;
 }
@@ -2267,6 +2551,7 @@ int gbls_g2_compress(const gbls_p2_affine *in, size_t n, uint8_t (*out)[96]) {
 // segmented aggregation of points (which = 1: G1, 2: G2) or of registry keys (which = 3)
 static int aggregate_impl(const void *pts, const uint32_t *idx, const uint32_t *seg_offsets,
                           size_t nseg, void *out, int32_t *status, int which) {
+  TEL_CALL(tel::K_DIRECT, 0, nseg);
   fill(status, nseg, GBLS_AGGR_TYPE_MISMATCH);
   API_BEGIN
   if (nseg == 0) return GBLS_SUCCESS;
@@ -2302,7 +2587,7 @@ static int aggregate_impl(const void *pts, const uint32_t *idx, const uint32_t *
       hipMemcpyAsync(status, c.out1.p, nseg * 4, hipMemcpyDeviceToHost, st) != hipSuccess)
     return fail(GBLS_ERR_HIP), FAILED;
   rl.unlock();  // enqueued: the host wait below does not hold up registry updates
-  if (hipStreamSynchronize(st) != hipSuccess) {
+  if (tel_stream_sync(L, st) != hipSuccess) {
     fill(status, nseg, GBLS_AGGR_TYPE_MISMATCH);
     return fail(GBLS_ERR_HIP), FAILED;
   }
@@ -2352,6 +2637,7 @@ int gbls_g2_aggregate(const gbls_p2_affine *sigs, size_t n, gbls_p2_affine *out)
 static int single_checks(const g2a *sigs, const uint8_t *msg_data, const uint32_t *msg_off,
                          const void *keys, const uint32_t *seg_off, size_t m, int mode,
                          int32_t *verdicts) {
+  TEL_CALL(tel::K_DIRECT, 0, m);
   fill(verdicts, m, GBLS_VERIFY_FAIL);
   API_BEGIN
   if (m == 0) return GBLS_SUCCESS;
@@ -2387,7 +2673,7 @@ static int single_checks(const g2a *sigs, const uint8_t *msg_data, const uint32_
   if (hipMemcpyAsync(verdicts, c.out1.p, m * 4, hipMemcpyDeviceToHost, st) != hipSuccess)
     return fail(GBLS_ERR_HIP), FAILED;
   rl.unlock();  // enqueued: the host wait does not hold up registry updates
-  if (hipStreamSynchronize(st) != hipSuccess) {
+  if (tel_stream_sync(L, st) != hipSuccess) {
     fill(verdicts, m, GBLS_VERIFY_FAIL);
     return fail(GBLS_ERR_HIP), FAILED;
   }
@@ -2405,6 +2691,7 @@ static int single_checks(const g2a *sigs, const uint8_t *msg_data, const uint32_
 static int single_checks_co(const uint8_t *msgs, const g2a *sigs, const uint8_t *sigs_c,
                             int32_t *sig_status, const g1a *pks, const uint32_t *pk_off, size_t m,
                             int32_t *verdicts) {
+  TEL_CALL(tel::K_CHECKS, 0, m);
   fill(verdicts, m, GBLS_VERIFY_FAIL);
   if (sig_status) fill(sig_status, m, GBLS_BAD_ENCODING);
   API_BEGIN
@@ -2492,6 +2779,7 @@ int gbls_fast_aggregate_verify(const gbls_p2_affine *sig, const uint8_t *msg, si
 int gbls_multi_verify_segments(const uint8_t (*msgs)[32], const gbls_p2_affine *sigs,
                                const gbls_p1_affine *pks, const uint64_t *rands, size_t n,
                                const uint32_t *seg_off, size_t nseg, int32_t *verdicts) {
+  TEL_CALL(tel::K_BATCH, 0, n);
   fill(verdicts, nseg, GBLS_VERIFY_FAIL);
   API_BEGIN
   if (nseg == 0) return GBLS_SUCCESS;
@@ -2508,6 +2796,7 @@ int gbls_multi_verify_segments(const uint8_t (*msgs)[32], const gbls_p2_affine *
 
 int gbls_multi_verify(const uint8_t (*msgs)[32], const gbls_p2_affine *sigs,
                       const gbls_p1_affine *pks, const uint64_t *rands, size_t n) {
+  TEL_CALL(tel::K_BATCH, 0, n);
   t_last_error = GBLS_ERR_NONE;  // the early verdicts below are verdicts, not engine errors
   if (n == 0) return GBLS_VERIFY_FAIL;
   for (size_t i = 0; i < n; i++)
@@ -2522,6 +2811,7 @@ int gbls_multi_verify(const uint8_t (*msgs)[32], const gbls_p2_affine *sigs,
 int gbls_multi_verify_indexed(const uint8_t (*msgs)[32], const gbls_p2_affine *sigs,
                               const uint32_t *pk_idx, const uint32_t *pk_off,
                               const uint64_t *rands, size_t n) {
+  TEL_CALL(tel::K_BATCH, 0, n);
   API_BEGIN
   if (n == 0) return GBLS_VERIFY_FAIL;
   if (pk_off && !valid_offsets(pk_off, n, pk_off[n])) return fail(GBLS_ERR_ARG), GBLS_VERIFY_FAIL;
@@ -2538,6 +2828,7 @@ int gbls_multi_verify_compressed_ex(const uint8_t (*msgs)[32], const uint8_t (*s
                                     const gbls_p1_affine *pks, const uint32_t *pk_idx,
                                     const uint32_t *pk_off, const uint64_t *rands, size_t n,
                                     int32_t *sig_status, uint32_t call_flags) {
+  TEL_CALL(tel::K_BATCH, (call_flags & GBLS_CALL_BLOCK) != 0, n);
   t_last_error = GBLS_ERR_NONE;
   if (!sig_status) return fail(GBLS_ERR_ARG), GBLS_VERIFY_FAIL;
   fill(sig_status, n, GBLS_BAD_ENCODING);
@@ -2575,6 +2866,7 @@ int gbls_multi_verify_bisect(const uint8_t (*msgs)[32], const gbls_p2_affine *si
                              const gbls_p1_affine *pks, const uint32_t *pk_idx,
                              const uint32_t *pk_off, const uint64_t *rands, size_t n,
                              int32_t *set_verdicts) {
+  TEL_CALL(tel::K_DIRECT, 0, n);
   fill(set_verdicts, n, GBLS_VERIFY_FAIL);
   API_BEGIN
   if (n == 0) return GBLS_SUCCESS;
@@ -2596,6 +2888,7 @@ int gbls_multi_verify_bisect(const uint8_t (*msgs)[32], const gbls_p2_affine *si
 static int device_verify(const uint8_t *msgs, const g2a *sigs, const PkSource &src,
                          const uint64_t *rands, size_t n, const uint32_t *seg_off, size_t nseg,
                          int32_t *verdicts, fp12 *partials, int32_t *seg_err, void *stream) {
+  TEL_CALL(tel::K_DEVICE, 0, n);
   API_BEGIN
   if (nseg == 0) return GBLS_SUCCESS;
   if (!valid_offsets(seg_off, nseg, n)) return fail(GBLS_ERR_ARG), FAILED;
@@ -2660,6 +2953,7 @@ int gbls_multi_verify_indexed_partials_device(const uint8_t *msgs, const gbls_p2
 
 int gbls_final_verify_partials_device(const gbls_fp12 *partials, const int32_t *seg_err,
                                       size_t nparts, size_t nseg, int32_t *verdicts, void *stream) {
+  TEL_CALL(tel::K_DEVICE, 0, nseg);
   API_BEGIN
   if (nseg == 0) return GBLS_SUCCESS;
   if (nparts == 0) return fail(GBLS_ERR_ARG), FAILED;
@@ -2679,6 +2973,7 @@ int gbls_final_verify_partials_device(const gbls_fp12 *partials, const int32_t *
 int gbls_fast_aggregate_verify_indexed_device(const gbls_p2_affine *sigs, const uint8_t *msgs,
                                               const uint32_t *pk_idx, const uint32_t *pk_off,
                                               size_t m, int32_t *verdicts, void *stream) {
+  TEL_CALL(tel::K_DEVICE, 0, m);
   API_BEGIN
   if (m == 0) return GBLS_SUCCESS;
   Device *d = current_device();
@@ -2718,6 +3013,7 @@ int gbls_fast_aggregate_verify_indexed_device(const gbls_p2_affine *sigs, const 
 // lock is released.  A failure truncates the registry to `first`, so no index can resolve to
 // replicas that disagree (indices past the size are BAD_ENCODING everywhere).
 int gbls_registry_set(size_t first, const uint8_t (*pks)[48], size_t n, int32_t *status) {
+  TEL_CALL(tel::K_DIRECT, 0, n);
   fill(status, n, GBLS_BAD_ENCODING);
   API_BEGIN
   std::vector<int32_t> st0(n);
@@ -2835,6 +3131,7 @@ size_t gbls_registry_size(void) {
 // any, are dropped.
 static int committees_set_impl(size_t first, const uint32_t *idx, const uint32_t *off, size_t ncom,
                                int32_t *status, bool keep) {
+  TEL_CALL(tel::K_DIRECT, 0, ncom);
   fill(status, ncom, GBLS_BAD_ENCODING);
   API_BEGIN
   if (first > kMaxCommittees || ncom > kMaxCommittees - first) return fail(GBLS_ERR_ARG), FAILED;
@@ -2963,6 +3260,7 @@ static bool committee_args_ok(const uint32_t *com, const uint32_t *pk_idx, const
 
 int gbls_g1_aggregate_committees(const uint32_t *com, const uint32_t *pk_idx, const uint32_t *pk_off,
                                  size_t n, gbls_p1_affine *out, int32_t *status) {
+  TEL_CALL(tel::K_DIRECT, 0, n);
   fill(status, n, GBLS_BAD_ENCODING);
   if (out) std::memset(out, 0, n * sizeof(*out));
   API_BEGIN
@@ -2986,7 +3284,7 @@ int gbls_g1_aggregate_committees(const uint32_t *com, const uint32_t *pk_idx, co
       hipMemcpyAsync(status, pre, n * 4, hipMemcpyDeviceToHost, st) != hipSuccess)
     return fail(GBLS_ERR_HIP), FAILED;
   rl.unlock();  // enqueued: the host wait below does not hold up registry updates
-  if (hipStreamSynchronize(st) != hipSuccess) {
+  if (tel_stream_sync(L, st) != hipSuccess) {
     fill(status, n, GBLS_BAD_ENCODING);
     std::memset(out, 0, n * sizeof(*out));
     return fail(GBLS_ERR_HIP), FAILED;
@@ -2998,6 +3296,7 @@ int gbls_multi_verify_committees(const uint8_t (*msgs)[32], const uint8_t (*sigs
                                  const uint32_t *com, const uint32_t *pk_idx, const uint32_t *pk_off,
                                  const uint64_t *rands, size_t n, int32_t *sig_status,
                                  uint32_t call_flags) {
+  TEL_CALL(tel::K_DIRECT, (call_flags & GBLS_CALL_BLOCK) != 0, n);
   t_last_error = GBLS_ERR_NONE;
   if (!sig_status) return fail(GBLS_ERR_ARG), GBLS_VERIFY_FAIL;
   fill(sig_status, n, GBLS_BAD_ENCODING);
@@ -3054,6 +3353,7 @@ static bool bits_args_ok(const uint32_t *com, const uint8_t *bits, const uint32_
 int gbls_g1_aggregate_bits(const uint32_t *com, const uint8_t *bits, const uint32_t *bits_off,
                            const uint32_t *pk_idx, const uint32_t *pk_off, size_t n, gbls_p1_affine *out,
                            int32_t *status) {
+  TEL_CALL(tel::K_DIRECT, 0, n);
   fill(status, n, GBLS_BAD_ENCODING);
   if (out) std::memset(out, 0, n * sizeof(*out));
   API_BEGIN
@@ -3079,7 +3379,7 @@ int gbls_g1_aggregate_bits(const uint32_t *com, const uint8_t *bits, const uint3
       hipMemcpyAsync(status, pre, n * 4, hipMemcpyDeviceToHost, st) != hipSuccess)
     return fail(GBLS_ERR_HIP), FAILED;
   rl.unlock();  // enqueued: the host wait below does not hold up registry updates
-  if (hipStreamSynchronize(st) != hipSuccess) {
+  if (tel_stream_sync(L, st) != hipSuccess) {
     fill(status, n, GBLS_BAD_ENCODING);
     std::memset(out, 0, n * sizeof(*out));
     return fail(GBLS_ERR_HIP), FAILED;
@@ -3091,6 +3391,7 @@ int gbls_multi_verify_bits(const uint8_t (*msgs)[32], const uint8_t (*sigs)[96],
                            const uint8_t *bits, const uint32_t *bits_off, const uint32_t *pk_idx,
                            const uint32_t *pk_off, const uint64_t *rands, size_t n, int32_t *sig_status,
                            uint32_t call_flags) {
+  TEL_CALL(tel::K_DIRECT, (call_flags & GBLS_CALL_BLOCK) != 0, n);
   t_last_error = GBLS_ERR_NONE;
   if (!sig_status) return fail(GBLS_ERR_ARG), GBLS_VERIFY_FAIL;
   fill(sig_status, n, GBLS_BAD_ENCODING);
@@ -3137,6 +3438,7 @@ static bool spans_args_ok(const uint32_t *com, const uint8_t (*cbits)[8], const 
 int gbls_g1_aggregate_spans(const uint32_t *com, const uint8_t (*cbits)[8], const uint8_t *bits,
                             const uint32_t *bits_off, const uint32_t *pk_idx, const uint32_t *pk_off, size_t n,
                             gbls_p1_affine *out, int32_t *status) {
+  TEL_CALL(tel::K_DIRECT, 0, n);
   fill(status, n, GBLS_BAD_ENCODING);
   if (out) std::memset(out, 0, n * sizeof(*out));
   API_BEGIN
@@ -3163,7 +3465,7 @@ int gbls_g1_aggregate_spans(const uint32_t *com, const uint8_t (*cbits)[8], cons
       hipMemcpyAsync(status, pre, n * 4, hipMemcpyDeviceToHost, st) != hipSuccess)
     return fail(GBLS_ERR_HIP), FAILED;
   rl.unlock();  // enqueued: the host wait below does not hold up registry updates
-  if (hipStreamSynchronize(st) != hipSuccess) {
+  if (tel_stream_sync(L, st) != hipSuccess) {
     fill(status, n, GBLS_BAD_ENCODING);
     std::memset(out, 0, n * sizeof(*out));
     return fail(GBLS_ERR_HIP), FAILED;
@@ -3175,6 +3477,7 @@ int gbls_multi_verify_spans(const uint8_t (*msgs)[32], const uint8_t (*sigs)[96]
                             const uint8_t (*cbits)[8], const uint8_t *bits, const uint32_t *bits_off,
                             const uint32_t *pk_idx, const uint32_t *pk_off, const uint64_t *rands, size_t n,
                             int32_t *sig_status, uint32_t call_flags) {
+  TEL_CALL(tel::K_DIRECT, (call_flags & GBLS_CALL_BLOCK) != 0, n);
   t_last_error = GBLS_ERR_NONE;
   if (!sig_status) return fail(GBLS_ERR_ARG), GBLS_VERIFY_FAIL;
   fill(sig_status, n, GBLS_BAD_ENCODING);
@@ -3214,6 +3517,7 @@ static int spans_checks_co(const uint8_t (*msgs)[32], const uint8_t (*sigs)[96],
                            const uint32_t *pk_idx, const uint32_t *pk_off, const uint64_t *rands, size_t n,
                            const uint32_t *seg_off, size_t nseg, int32_t *sig_status, int32_t *key_status,
                            int32_t *verdicts, uint32_t call_flags, bool each, const PkSource *fold = nullptr) {
+  TEL_CALL(each ? (fold ? tel::K_FOLD : tel::K_SPAN_CHECKS) : tel::K_SPAN_ITEMS, (call_flags & GBLS_CALL_BLOCK) != 0, n);
   // (a group count that does not fit 32 bits names no array to fill)
   const size_t nfold = fold && (uint64_t)fold->nfold < 0xffffffffull ? fold->nfold : 0;
   auto prefill = [&] {
@@ -3323,6 +3627,7 @@ int gbls_g1_aggregate_local(const uint32_t *com, const uint8_t (*cbits)[8], cons
                             const uint32_t *bits_off, const uint32_t *pk_idx, const uint32_t *pk_off,
                             const uint8_t (*pkb)[48], size_t npkb, size_t n, gbls_p1_affine *out, int32_t *status,
                             int32_t *pkb_status) {
+  TEL_CALL(tel::K_DIRECT, 0, n);
   const bool table_ok = (uint64_t)npkb <= 0xffffffffull;  // (a count that does not fit names no array to fill)
   auto prefill = [&] {
     fill(status, n, GBLS_BAD_ENCODING);
@@ -3360,7 +3665,7 @@ int gbls_g1_aggregate_local(const uint32_t *com, const uint8_t (*cbits)[8], cons
       hipMemcpyAsync(pkb_status, c.locst.p, npkb * 4, hipMemcpyDeviceToHost, st) != hipSuccess)
     return fail(GBLS_ERR_HIP), FAILED;
   rl.unlock();  // enqueued: the host wait below does not hold up registry updates
-  if (hipStreamSynchronize(st) != hipSuccess) {
+  if (tel_stream_sync(L, st) != hipSuccess) {
     prefill();
     return fail(GBLS_ERR_HIP), FAILED;
   }
@@ -3374,6 +3679,7 @@ static int local_checks_co(const uint8_t (*msgs)[32], const uint8_t (*sigs)[96],
                            const uint64_t *rands, size_t n, const uint32_t *seg_off, size_t nseg, int32_t *sig_status,
                            int32_t *key_status, int32_t *verdicts, int32_t *pkb_status, uint32_t call_flags,
                            bool each) {
+  TEL_CALL(each ? tel::K_LOCAL_CHECKS : tel::K_LOCAL_ITEMS, (call_flags & GBLS_CALL_BLOCK) != 0, n);
   const bool table_ok = (uint64_t)npkb <= 0xffffffffull;
   auto prefill = [&] {
     if (verdicts) fill(verdicts, nseg, GBLS_VERIFY_FAIL);
@@ -3525,6 +3831,7 @@ static bool prefetch_enqueue(Ctx &c, const msgcache::DevicePrefetch &dp, uint32_
 }
 
 int gbls_msgcache_prefetch(const uint8_t (*msgs)[32], size_t n, int32_t *status) {
+  TEL_CALL(tel::K_DIRECT, 0, n);
   if (status) fill(status, n, GBLS_PREFETCH_SKIPPED);
   t_last_error = GBLS_ERR_NONE;
   if (n == 0) return GBLS_SUCCESS;
@@ -3584,6 +3891,7 @@ int gbls_msgcache_prefetch(const uint8_t (*msgs)[32], size_t n, int32_t *status)
 }
 
 int gbls_sk_to_pk(const uint8_t (*sks)[32], size_t n, gbls_p1_affine *out) {
+  TEL_CALL(tel::K_DIRECT, 0, n);
   API_BEGIN
   if (n == 0) return GBLS_SUCCESS;
   Lease L(pick_device());
@@ -3594,7 +3902,7 @@ int gbls_sk_to_pk(const uint8_t (*sks)[32], size_t n, gbls_p1_affine *out) {
     return FAILED;
   launch_sk_to_pk(st, c.in0.as<uint8_t>(), (uint32_t)n, c.out0.as<g1a>());
   if (hipMemcpyAsync(out, c.out0.p, n * sizeof(g1a), hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess)
+      tel_stream_sync(L, st) != hipSuccess)
     return fail(GBLS_ERR_HIP), FAILED;
   return GBLS_SUCCESS;
 }
@@ -3615,6 +3923,7 @@ static bool h2c_affine(Ctx &c, const uint8_t *msg_data, const uint32_t *msg_off,
 
 int gbls_sign(const uint8_t (*sks)[32], const uint8_t *msg_data, const uint32_t *msg_off, size_t n,
               gbls_p2_affine *out) {
+  TEL_CALL(tel::K_DIRECT, 0, n);
   API_BEGIN
   if (n == 0) return GBLS_SUCCESS;
   Lease L(pick_device());
@@ -3626,13 +3935,14 @@ int gbls_sign(const uint8_t (*sks)[32], const uint8_t *msg_data, const uint32_t 
   if (!h2c_affine(c, msg_data, msg_off, n, nullptr, 0, st)) return FAILED;
   launch_sign(st, c.in0.as<uint8_t>(), c.out1.as<g2a>(), (uint32_t)n, c.out0.as<g2a>());
   if (hipMemcpyAsync(out, c.out0.p, n * sizeof(g2a), hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess)
+      tel_stream_sync(L, st) != hipSuccess)
     return fail(GBLS_ERR_HIP), FAILED;
   return GBLS_SUCCESS;
 }
 
 int gbls_hash_to_g2(const uint8_t *msg_data, const uint32_t *msg_off, size_t n, const uint8_t *dst,
                     size_t dst_len, gbls_p2_affine *out) {
+  TEL_CALL(tel::K_DIRECT, 0, n);
   API_BEGIN
   if (n == 0) return GBLS_SUCCESS;
   // dst == NULL (with dst_len 0): the signature scheme's own DST (BLS_SIG_..._POP_)
@@ -3645,7 +3955,7 @@ int gbls_hash_to_g2(const uint8_t *msg_data, const uint32_t *msg_off, size_t n, 
   if (!h2c_affine(c, msg_data, msg_off, n, dst ? c.in3.as<uint8_t>() : nullptr, (uint32_t)dst_len, st))
     return FAILED;
   if (hipMemcpyAsync(out, c.out1.p, n * sizeof(g2a), hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess)
+      tel_stream_sync(L, st) != hipSuccess)
     return fail(GBLS_ERR_HIP), FAILED;
   return GBLS_SUCCESS;
 }
@@ -3721,5 +4031,82 @@ void gbls_profile_reset(void) {
 const char *gbls_stage_name(int stage) {
   return (stage >= 0 && stage < S_COUNT) ? kStageNames[stage] : "";
 }
+
+// ---- include/grandine_bls_gpu_telemetry.h
+int gbls_telemetry_enable(int level) {
+  level = level < 0 ? 0 : level > 2 ? 2 : level;
+  const int prev = g_tel.level.exchange(level, std::memory_order_relaxed);
+  // level 2: the timing events of every engine device at hand before the first timed call
+  if (level >= 2 && g.ready.load())
+    for (auto &dp : g.devs) (void)dp->tel_fill(kTelEvents);
+  return prev;
+}
+
+int gbls_telemetry_read(gbls_telemetry_snapshot *out, size_t size) {
+  t_last_error = GBLS_ERR_NONE;
+  if (!out || size < 8) return fail(GBLS_ERR_ARG), FAILED;
+  static std::mutex mu;  // readers only: the snapshot buffer
+  static gbls_telemetry_snapshot snap;
+  std::lock_guard<std::mutex> lk(mu);
+  g_tel.read(snap);
+  const size_t k = std::min(size, sizeof(snap));
+  snap.size = (uint32_t)k;
+  std::memcpy(out, &snap, k);
+  return GBLS_SUCCESS;
+}
+
+void gbls_telemetry_reset(void) { g_tel.reset(); }
+
+size_t gbls_telemetry_trace(gbls_telemetry_record *records, size_t max, uint64_t *dropped) {
+  if (dropped) *dropped = 0;
+  if (!records || !max) return 0;
+  return g_tel.ring.drain(records, max, dropped);
+}
+
+int gbls_telemetry_memory(gbls_telemetry_memory_info *out, size_t size) {
+  t_last_error = GBLS_ERR_NONE;
+  if (!out || size < 8) return fail(GBLS_ERR_ARG), FAILED;
+  std::unique_ptr<gbls_telemetry_memory_info> m(new gbls_telemetry_memory_info());
+  if (g.ready.load()) {
+    int cur = -1;
+    (void)hipGetDevice(&cur);
+    std::shared_lock<std::shared_mutex> rl(g.reg_mu);
+    for (auto &dp : g.devs) {
+      if (m->engines >= GBLS_TELEMETRY_MAX_ENGINES) break;
+      Device &d = *dp;
+      gbls_telemetry_engine_memory &e = m->engine[m->engines++];
+      e.hip_device = (uint32_t)d.hipdev;
+      d.pool.for_each([&](Ctx &c) {
+        const int k = c.cls ? 1 : 0;
+        (c.leased.load(std::memory_order_relaxed) ? e.contexts_leased : e.contexts_idle)[k]++;
+        e.workspace_bytes[k] += c.ws_bytes.load(std::memory_order_relaxed);
+        e.pinned_live_bytes += c.pinned_live.load(std::memory_order_relaxed);
+        e.pinned_retired_bytes += c.pinned_retired.load(std::memory_order_relaxed);
+        e.pinned_retired_buffers += c.pinned_retired_n.load(std::memory_order_relaxed);
+      });
+      e.registry_bytes = d.reg.cap;
+      e.committee_bytes = d.com.cap;
+      for (const Device::MemBlock &mb : d.mem_blocks) e.member_bytes += mb.p ? mb.bytes : 0;
+      {
+        std::lock_guard<std::mutex> lk(mcache.mu);
+        e.linecache_bytes = d.mc_tab && d.mc_tab->dev ? d.mc_tab->bytes : 0;
+      }
+      size_t fr = 0, tot = 0;
+      if (hipSetDevice(d.hipdev) == hipSuccess && hipMemGetInfo(&fr, &tot) == hipSuccess)
+        e.device_free_bytes = fr, e.device_total_bytes = tot;
+      else
+        (void)hipGetLastError();
+    }
+    if (cur >= 0) (void)hipSetDevice(cur);
+  }
+  const size_t k = std::min(size, sizeof(*m));
+  m->size = (uint32_t)k;
+  std::memcpy(out, m.get(), k);
+  return GBLS_SUCCESS;
+}
+
+const char *gbls_telemetry_phase_name(int i) { return tel::phase_name(i); }
+const char *gbls_telemetry_kind_name(int i) { return tel::kind_name(i); }
+const char *gbls_telemetry_class_name(int i) { return tel::class_name(i); }
 
 }  // extern "C"

@@ -188,6 +188,20 @@ inline void local_rebase(uint32_t *idx, const uint32_t *off, const uint32_t *com
   }
 }
 
+// Telemetry (gbls_telemetry.h), written only for a request that carries `ph` under a Config that
+// carries `clock`: when the caller entered submit, how long it was held and how long it sat in a
+// collection window, when its submission started (the same for every member of a batch) and how
+// long that ran.  What is left of lead_ns - submit_ns after hold and window is the time queued.
+struct CallPhases {
+  uint64_t submit_ns = 0, hold_ns = 0, window_ns = 0, lead_ns = 0, run_ns = 0;
+};
+// ... and what the verifier may read about the batch it is handed (Request::bi of the merged request)
+struct BatchInfo {
+  uint64_t first_arrival_ns = 0, lead_ns = 0;  // earliest submit_ns of the members; start of the submission
+  uint32_t callers = 0;
+  uint64_t sets = 0;
+};
+
 // One caller's batch (host pointers, borrowed for the call).  rands == nullptr: independent
 // single checks (Signature::verify / fast_aggregate_verify semantics: r_i = 1, the
 // signature's subgroup check, one segment per set), merged only with other single checks.
@@ -210,6 +224,8 @@ struct Request {
   int prio = 0;                     // 1: block import
   bool done = false, ok = false;
   int err = 0;                      // the verifier's side-channel error code
+  CallPhases *ph = nullptr;         // telemetry: this caller's phases (null: none recorded)
+  const BatchInfo *bi = nullptr;    // telemetry: the batch this request runs in (set by submit)
   bool spans() const { return src.cbits != nullptr; }
   // A span source (com, cbits, bits, bits_off; idx and off for its plain sets, off == nullptr
   // when it has none) is a kind of its own whether or not it carries index ranges; a local
@@ -236,6 +252,9 @@ struct Config {
   // submissions already running (null: never hold)
   const std::atomic<int> *hold = nullptr;
   int hold_max_us = 4000;
+  // telemetry: the clock (ns) that stamps the requests carrying Request::ph; null (the default)
+  // or a request without ph: nothing is stamped and no clock is read
+  uint64_t (*clock)() = nullptr;
 };
 
 // Runs the requests of `batch` (all of one kind) as ONE segmented verification: the merged
@@ -268,7 +287,17 @@ void run_merged(std::vector<Req *> &batch, Verify &&verify) {
     nent += fold && r->src.nfold ? r->src.fold_off[r->src.nfold] : 0;
   }
   if (nloc > 0xffffffffull || ngrp >= 0xffffffffull || nent > 0xffffffffull) {
-    for (Req *r : batch) verify(*r);
+    for (Req *r : batch) {
+      BatchInfo one;  // each request is then a submission of its own
+      if (r->bi) {
+        one = *r->bi;
+        one.callers = 1;
+        one.sets = r->n;
+        r->bi = &one;
+      }
+      verify(*r);
+      r->bi = nullptr;
+    }
     return;
   }
   using G1 = typename Req::g1_type;
@@ -385,6 +414,7 @@ void run_merged(std::vector<Req *> &batch, Verify &&verify) {
     m.src.fold_count = fcnt.data();
   }
   m.prio = r0.prio;
+  m.bi = r0.bi;
   verify(m);
   sat = 0;
   at = 0;
@@ -422,8 +452,19 @@ class Coalescer {
  public:
   template <class Verify>
   bool submit(Req &r, const Config &cfg, Verify &&verify) {
+    const bool tel = cfg.clock && r.ph;
+    if (tel) r.ph->submit_ns = cfg.clock();
     if (!cfg.coalesce) {
+      BatchInfo bi;
+      if (tel) {
+        bi.first_arrival_ns = bi.lead_ns = r.ph->lead_ns = r.ph->submit_ns;
+        bi.callers = 1;
+        bi.sets = r.n;
+        r.bi = &bi;
+      }
       verify(r);
+      r.bi = nullptr;
+      if (tel) r.ph->run_ns = cfg.clock() - r.ph->lead_ns;
       return r.ok;
     }
     const int max_leaders = (r.prio ? 1 : cfg.leaders) * std::max(1, cfg.devices);
@@ -437,9 +478,14 @@ class Coalescer {
     while (!r.done) {
       if (!r.prio && !held && cfg.hold && cfg.hold->load() > 0) {
         held = true;  // a block import is being verified: leave it the GPU for a while
+        const uint64_t t0 = tel ? cfg.clock() : 0;
         const auto deadline =
             std::chrono::steady_clock::now() + std::chrono::microseconds(cfg.hold_max_us);
         cv_.wait_until(lk, deadline, [&] { return r.done || cfg.hold->load() == 0; });
+        if (tel) {  // (done: it ended with the submission's start -- if that leader stamped it)
+          const uint64_t t1 = r.done ? r.ph->lead_ns : cfg.clock();
+          if (t1 >= t0) r.ph->hold_ns += t1 - t0;
+        }
         continue;
       }
       if (leaders < max_leaders && !q.empty()) {
@@ -454,9 +500,14 @@ class Coalescer {
         };
         if (!r.prio && leaders > 0 && !waited && queued() < cfg.merge_target) {
           waited = true;
+          const uint64_t t0 = tel ? cfg.clock() : 0;
           const auto deadline =
               std::chrono::steady_clock::now() + std::chrono::microseconds(cfg.merge_window_us);
           cv_.wait_until(lk, deadline, [&] { return r.done || queued() >= cfg.merge_target; });
+          if (tel) {
+            const uint64_t t1 = r.done ? r.ph->lead_ns : cfg.clock();
+            if (t1 >= t0) r.ph->window_ns += t1 - t0;
+          }
           continue;
         }
         leaders++;
@@ -478,8 +529,33 @@ class Coalescer {
             ++it;
           }
         }
+        // telemetry: the members that carry phases share the submission's start and duration
+        BatchInfo bi;
+        bool stamped = false;
+        for (Req *b : batch) stamped = stamped || b->ph;
+        stamped = stamped && cfg.clock;
+        if (stamped) {
+          bi.lead_ns = cfg.clock();
+          bi.first_arrival_ns = bi.lead_ns;
+          bi.callers = (uint32_t)batch.size();
+          bi.sets = sets;
+          for (Req *b : batch) {
+            if (b->ph) {
+              b->ph->lead_ns = bi.lead_ns;
+              bi.first_arrival_ns = std::min(bi.first_arrival_ns, b->ph->submit_ns);
+            }
+            b->bi = &bi;
+          }
+        }
         lk.unlock();
         run_merged(batch, verify);  // writes verdicts, ok, err; `done` is published under mu_
+        if (stamped) {
+          const uint64_t ran = cfg.clock() - bi.lead_ns;
+          for (Req *b : batch) {
+            if (b->ph) b->ph->run_ns = ran;
+            b->bi = nullptr;
+          }
+        }
         lk.lock();
         for (Req *b : batch) b->done = true;
         leaders--;

@@ -32,11 +32,13 @@ pub mod ffi_local;
 pub mod ffi_msgcache;
 pub mod ffi_msgcache_checks;
 pub mod ffi_spans;
+pub mod ffi_telemetry;
 pub mod fold;
 pub mod local;
 pub mod msgcache;
 pub mod msgcache_checks;
 pub mod spans;
+pub mod telemetry;
 
 use core::{ffi::c_int, ptr};
 use std::sync::OnceLock;
@@ -149,7 +151,8 @@ static ENGINE: OnceLock<EngineResult<usize>> = OnceLock::new();
 /// `GBLS_NO_COALESCE=1` turns cross-caller coalescing off; `GBLS_DEDUP=1` groups the sets of a
 /// batch by message (`GBLS_INIT_DEDUP`: one hash and one pairing per distinct message, verdicts
 /// unchanged).  All three are sticky in the library, so no later initialisation clears them
-/// (see also [`set_policy`]).
+/// (see also [`set_policy`]).  `GBLS_TELEMETRY=1` (or `2`) switches engine telemetry on before the
+/// engine opens (see [`telemetry`]).
 pub fn engine() -> EngineResult<usize> {
     *ENGINE.get_or_init(|| {
         let mask = std::env::var("GBLS_DEVICE_MASK")
@@ -170,6 +173,10 @@ pub fn engine() -> EngineResult<usize> {
         }
         if on("GBLS_DEDUP") {
             flags |= ffi::GBLS_INIT_DEDUP;
+        }
+        // `GBLS_TELEMETRY=1|2`: engine telemetry on from the start (telemetry.rs)
+        if let Some(level) = telemetry::level_from_env() {
+            telemetry::enable(level);
         }
         // SAFETY: plain integers in; the library serialises its own initialisation.
         let rc = unsafe { ffi::gbls_init(mask, flags) };
